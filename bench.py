@@ -9,7 +9,10 @@ All inputs are synthetic, resident in HBM before the timed regi
 HIP graph (--steps-per-graph consecutive steps per graph launch, every step complete) and replayed.  Multi-GPU: one process per GPU, independent sequences (seed 1234 + rank), no data-path
 collective (replicas; "scaling": "weak"); the aggregate is steps*ranks / max-over-ranks time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dtype f32|f16]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2] [--dtype f32|f16] [--dump-outputs DIR] [--full]
+
+A plain run prints the headline line only; --full adds every other figure and check (roofline, fastba report, the fp16 second
+measurement, the reference call sequence, the CPU baseline, ...).  --dump-outputs DIR writes the last timed step's outputs as .npy.
 """
 import argparse
 import json
@@ -91,9 +94,35 @@ def parse():
                     help="skip the extra field full_update_iteration: a FULL DEVO update iteration — the step with the Update operator "
                          "(devo_amd.update, random weights, fp32 and fp16) between lookup and BA, feeding delta / weight to the BA (the "
                          "headline metric excludes the Update MLP, SURVEY 8d)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure (off by default: a plain run sets up, warms up, times "
+                         "--steps steps and prints the line): the lookup roofline and fastba report, the plan-in-line and new-graph-every-step "
+                         "variants, the full update iteration, the fp16 second measurement, the reference call sequence, the CPU baseline and, "
+                         "with --gpus N > 1, the data-parallel training probe (each still switched off by its --no-* option).  --with-stress implies it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy (float32 / float64): "
+                         "update-op: poses, patches (after the BA), coords (the reprojection), corr + corr_edges (the lookup's output for a fixed, "
+                         "seeded sample of edges); train: loss.  Rank 0's outputs; the inputs are the same from run to run")
     args = ap.parse_args()
     args.fuse_levels = not args.per_level_launches
+    if args.with_stress:
+        args.full = True
+    if args.dump_outputs and args.mode == "update-op" and args.api == "reference":
+        ap.error("--dump-outputs: the --api reference probe is not a timed path of its own")
     return args
+
+
+DUMP_BYTES = 32 << 20          # --dump-outputs: at most this many bytes of lookup output (a seeded sample of edges), well under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: every array as path/<name>.npy, float64 kept, everything else as float32."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().cpu()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(path, name + ".npy"), t.numpy())
 
 
 def build_inputs(cfg, seed, device, dtype, layout):
@@ -238,6 +267,8 @@ def train_mode(args, device, rank, world, steps=None, warmup=None, iters=None, p
            "grad_bucket_bytes": 4 * nparam, "parameters": nparam, "collective": (("DDP all-reduce (gloo: --share-gpu debug run)" if getattr(args, "share_gpu", False) else "DDP all-reduce (RCCL)") if ddp else None)}
     if probe:
         return res
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": torch.tensor([float(loss)], dtype=torch.float64)})
     return {"metric": "training sequences/sec (update + BA path, batch = 1 sequence per GPU)", "value": res["sequences_per_s"], "unit": "seq/s",
             "n_gpus": world, "steps": steps, "warmup": warmup, "ms_per_step": res["ms_per_step"], "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
@@ -524,6 +555,7 @@ def update_op_mode(args, device, rank, world, dtype_name=None, secondary=False):
         probe["ev"].append((a, b))
 
     plan_prev = [None]                                                   # the finished plan of the previous step (--plan-lag 1)
+    last = {}                                                            # the reprojected coordinates of the last step() call
 
     def step(k=0, every=None, lag=None):
         cur = torch.cuda.current_stream()
@@ -540,6 +572,7 @@ def update_op_mode(args, device, rank, world, dtype_name=None, secondary=False):
         # reprojection; the kernel also emits the lookup's plan bins while it holds the coordinates
         coords, order = cuda_ba.transform(d["poses"], d["patches"], d["intr"], d["ii"], d["jj"], d["kk"], layout="2pp",
                                           plan_for=(n, cfg["H"], R, cfg["W"], PL1))
+        last["coords"] = coords                                            # (--dump-outputs: a graph replay rewrites the captured tensor)
         own_plan = order                                                   # this step's plan buffer (bins written, not yet ordered)
         if lagged:
             order = plan_prev[0]                                           # (own_plan is ordered by this step's BA, for the next step)
@@ -584,13 +617,15 @@ def update_op_mode(args, device, rank, world, dtype_name=None, secondary=False):
             torch.cuda.synchronize()
             with torch.cuda.graph(graph, stream=side):
                 step()
+            coords_one = last["coords"]
             gmany = None
             if args.steps_per_graph > 1:                                   # several consecutive steps in one graph launch
                 gmany = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(gmany, stream=side):
                     for k in range(args.steps_per_graph):
                         step(k)
-                if args.prepare_every > 1 and not secondary:               # the same steps with a NEW patch graph in every one of them
+                coords_many = last["coords"]
+                if args.prepare_every > 1 and not secondary and args.full:  # the same steps with a NEW patch graph in every one of them
                     gevery = torch.cuda.CUDAGraph()
                     with torch.cuda.graph(gevery, stream=side):
                         for k in range(args.steps_per_graph):
@@ -633,6 +668,37 @@ def update_op_mode(args, device, rank, world, dtype_name=None, secondary=False):
         elapsed = samples[len(samples) // 2]
     ms_per_step = 1e3 * elapsed / args.steps
     value = world * args.steps / elapsed
+    if args.dump_outputs and rank == 0 and not secondary:
+        # what the last timed step computed (every step starts from the same state, so it is what each of them computed): the BA's poses
+        # and patches, the reprojection, and the lookup's output for a fixed, seeded sample of edges (the whole of it is 76 MB at cfg2)
+        if args.no_graph or gmany is None or not (n_many > 0 and args.steps == n_many * args.steps_per_graph):
+            c_last = last["coords"] if args.no_graph else coords_one
+        else:
+            c_last = coords_many
+        ns = min(E, max(1, DUMP_BYTES // (corr_out[0, 0].numel() * 4)))
+        sel = torch.randperm(E, generator=torch.Generator().manual_seed(0))[:ns].sort().values
+        torch.cuda.synchronize()
+        dump_outputs(args.dump_outputs, {"poses": d["poses"], "patches": d["patches"], "coords": c_last,
+                                         "corr": corr_out[0, sel.to(device)], "corr_edges": sel.double()})
+    out = {
+        "metric": "update-op iterations/sec (altcorr+fastba) at 96 patches, N=15 keyframes",
+        "value": round(value, 2), "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 4), "timed_regions": regions, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": dtn, "data": "synthetic",
+        "config": {"workload": f"{args.workload}: M={M} patches/frame, n={n} keyframes, E={E} edges, r={R}, "
+                               f"2 pyramid levels {cfg['H']}x{cfg['W']} + /4, C={cfg['C']}, 2 GN iterations, "
+                               f"pyramid layout {args.layout}, {'both levels in one lookup launch' if args.fuse_levels else 'one lookup launch per level'}, "
+                               f"{('HIP graph, ' + str(args.steps_per_graph) + ' step(s) per graph launch') if not args.no_graph else 'eager'}"
+                               f"{', BA index preparation on a second stream' if args.overlap_prepare else ''}",
+                   "parallelism": f"replicas x{world}" + (" (debug: all ranks on ONE GPU, --share-gpu)" if args.share_gpu else "")},
+    }
+    out["config"]["ba_index_tables"] = f"rebuilt every {args.prepare_every} steps (one patch graph = {args.prepare_every} update iterations)"
+    out["config"]["lookup_plan"] = ("on an unchanged patch graph the lookup runs under the plan made from the previous iteration's coordinates; its ordering "
+                                    "step rides on the BA's first solver launch (cuda_ba.forward_delta(..., plan_next=...)); a new patch graph orders its plan in line"
+                                    if (args.plan_lag and not (args.separate_target or args.separate_index_kernels or args.overlap_prepare))
+                                    else "ordered in line by every step, in front of its lookup")
+    if not args.full:
+        return out                                                         # a plain run: the headline figure only (everything below: --full)
     ms_every = None
     if gevery is not None:                                                 # every step rebuilds the BA's index tables (rounds 1-5's step)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -765,42 +831,25 @@ def update_op_mode(args, device, rank, world, dtype_name=None, secondary=False):
     except (OSError, ValueError, KeyError):
         pass
 
-    out = {
-        "metric": "update-op iterations/sec (altcorr+fastba) at 96 patches, N=15 keyframes",
-        "value": round(value, 2), "unit": "it/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 4), "timed_regions": regions, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": dtn, "data": "synthetic",
-        "config": {"workload": f"{args.workload}: M={M} patches/frame, n={n} keyframes, E={E} edges, r={R}, "
-                               f"2 pyramid levels {cfg['H']}x{cfg['W']} + /4, C={cfg['C']}, 2 GN iterations, "
-                               f"pyramid layout {args.layout}, {'both levels in one lookup launch' if args.fuse_levels else 'one lookup launch per level'}, "
-                               f"{('HIP graph, ' + str(args.steps_per_graph) + ' step(s) per graph launch') if not args.no_graph else 'eager'}"
-                               f"{', BA index preparation on a second stream' if args.overlap_prepare else ''}",
-                   "parallelism": f"replicas x{world}" + (" (debug: all ranks on ONE GPU, --share-gpu)" if args.share_gpu else "")},
-        "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
-                     "kernel": lookup_kernel,
-                     # the FMA ceiling beside the HBM figure.  F_alg = 2 * C * E * 9 * D^2 per level; fp32 peak
-                     # 157.3 TFLOP/s (vector FMA and fp32 MFMA alike); t_min = max(B_alg / HBM peak, F_alg / fp32 peak)
-                     "alg_gflop_per_launch": round(f_alg / 1e9, 3), "achieved_tflops": round(f_alg / t_launch / 1e12, 2),
-                     "t_min_us": round(max(b_alg / (HBM_PEAK_GBS * 1e9), f_alg / 157.3e12) * 1e6, 1),
-                     "alg_bytes_per_launch": int(b_alg), "us_per_launch": round(t_launch * 1e6, 2),
-                     "us_per_launch_back_to_back": round(t_back_to_back * 1e6, 2), "us_per_launch_in_step_raw": round(t_in_step * 1e6, 2),
-                     "event_pair_us": round(t_event_pair * 1e6, 2),
-                     "frac_back_to_back": round(b_alg / t_back_to_back / 1e9 / HBM_PEAK_GBS, 4),
-                     "timing": "achieved / frac / us_per_launch: HIP events around the lookup launch of " + str(args.kernel_reps) + " eager steps (the kernel where the step runs "
-                               "it, nothing subtracted: the pair of events itself costs event_pair_us); back_to_back: events around " + str(args.kernel_reps) +
-                               " lookup launches replayed back to back from a HIP graph"},
-        "ba": dict({"gpu_ms": round(t_ba_gpu * 1e3, 4), "gpu_ms_new_graph": round(t_ba_gpu_new * 1e3, 4),
-                    "note": "gpu_ms / launches / kernels: cuda_ba.forward (2 GN iterations) on an unchanged kk — the index tables (unique patches, edges grouped by patch) "
-                            "come from forward()'s prepared-table cache; gpu_ms_new_graph: every call rebuilds them (one more launch)"},
-                   **ba_kernel_report(run_ba=lambda: cuda_ba.forward(
-                       d["poses"], d["patches"], d["intr"], tgt, d["weight"], d["lmbda"], d["ii"], d["jj"], d["kk"], 1, n, 2, ws=ws))),
-    }
-    out["config"]["ba_index_tables"] = f"rebuilt every {args.prepare_every} steps (one patch graph = {args.prepare_every} update iterations)"
-    out["config"]["lookup_plan"] = ("on an unchanged patch graph the lookup runs under the plan made from the previous iteration's coordinates; its ordering "
-                                    "step rides on the BA's first solver launch (cuda_ba.forward_delta(..., plan_next=...)); a new patch graph orders its plan in line"
-                                    if (args.plan_lag and not (args.separate_target or args.separate_index_kernels or args.overlap_prepare))
-                                    else "ordered in line by every step, in front of its lookup")
+    out["roofline"] = {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic, "traffic_source": traffic_src,
+                       "kernel": lookup_kernel,
+                       # the FMA ceiling beside the HBM figure.  F_alg = 2 * C * E * 9 * D^2 per level; fp32 peak
+                       # 157.3 TFLOP/s (vector FMA and fp32 MFMA alike); t_min = max(B_alg / HBM peak, F_alg / fp32 peak)
+                       "alg_gflop_per_launch": round(f_alg / 1e9, 3), "achieved_tflops": round(f_alg / t_launch / 1e12, 2),
+                       "t_min_us": round(max(b_alg / (HBM_PEAK_GBS * 1e9), f_alg / 157.3e12) * 1e6, 1),
+                       "alg_bytes_per_launch": int(b_alg), "us_per_launch": round(t_launch * 1e6, 2),
+                       "us_per_launch_back_to_back": round(t_back_to_back * 1e6, 2), "us_per_launch_in_step_raw": round(t_in_step * 1e6, 2),
+                       "event_pair_us": round(t_event_pair * 1e6, 2),
+                       "frac_back_to_back": round(b_alg / t_back_to_back / 1e9 / HBM_PEAK_GBS, 4),
+                       "timing": "achieved / frac / us_per_launch: HIP events around the lookup launch of " + str(args.kernel_reps) + " eager steps (the kernel where the step runs "
+                                 "it, nothing subtracted: the pair of events itself costs event_pair_us); back_to_back: events around " + str(args.kernel_reps) +
+                                 " lookup launches replayed back to back from a HIP graph"}
+    out["ba"] = dict({"gpu_ms": round(t_ba_gpu * 1e3, 4), "gpu_ms_new_graph": round(t_ba_gpu_new * 1e3, 4),
+                      "note": "gpu_ms / launches / kernels: cuda_ba.forward (2 GN iterations) on an unchanged kk — the index tables (unique patches, edges grouped by patch) "
+                              "come from forward()'s prepared-table cache; gpu_ms_new_graph: every call rebuilds them (one more launch)"},
+                     **ba_kernel_report(run_ba=lambda: cuda_ba.forward(
+                         d["poses"], d["patches"], d["intr"], tgt, d["weight"], d["lmbda"], d["ii"], d["jj"], d["kk"], 1, n, 2, ws=ws)))
     if ms_inline is not None:
         out["plan_in_line"] = {"ms_per_step": round(ms_inline, 4), "value": round(world * 1e3 / ms_inline, 2), "unit": "it/s",
                                "same_method_with_the_lagged_plan": {"ms_per_step": round(ms_lag_ev, 4), "value": round(world * 1e3 / ms_lag_ev, 2),

@@ -35,7 +35,7 @@ def _keep(name, line):
 
 
 def test_update_op_bench_on_two_ranks_sharing_the_gpu():
-    d, line = _run(["--gpus", "2", "--share-gpu", "--steps", "20", "--warmup", "5", "--no-f16"], timeout=900)
+    d, line = _run(["--gpus", "2", "--share-gpu", "--steps", "20", "--warmup", "5", "--no-f16", "--full"], timeout=900)
     _keep("bench_gpus2_share.json", line)
     assert d["n_gpus"] == 2 and d["steps"] == 20 and d["scaling"] == "weak"
     assert "x2" in d["config"]["parallelism"] or "2" in d["config"]["parallelism"]
@@ -53,7 +53,7 @@ def test_eight_ranks_first_call_work_stays_inside_the_probe_bound():
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.pop("DEVO_BENCH_PROBE_TIMEOUT", None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--steps", "18", "--warmup", "2", "--no-f16", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--share-gpu", "--steps", "18", "--warmup", "2", "--no-f16", "--no-cpu-baseline", "--full"],
                        env=env, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-1500:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -148,7 +148,7 @@ def test_multi_gpu_update_op_line_skips_the_single_gpu_probes():
     (rank 0 would hold the other ranks in the final barrier), the training probe bounded by DEVO_BENCH_PROBE_TIMEOUT (90 s by default)."""
     import time
     t0 = time.time()
-    d, _ = _run(["--gpus", "2", "--share-gpu", "--steps", "20", "--warmup", "5"], timeout=600)
+    d, _ = _run(["--gpus", "2", "--share-gpu", "--steps", "20", "--warmup", "5", "--full"], timeout=600)
     assert "reference_api" not in d and "full_update_iteration" not in d and "cpu_baseline" not in d
     assert "f16" in d and "train_dp" in d
     assert time.time() - t0 < 300

@@ -1,4 +1,4 @@
-for cb in 8 4 16; do for dt in f32 f16; do echo "cb=$cb $dt"; DEVO_BENCH_CB=$cb timeout 300 python bench.py --no-cpu-baseline --no-reference-api --no-f16 --dtype $dt --steps 100 --warmup 10 2>&1 | python -c "
+for cb in 8 4 16; do for dt in f32 f16; do echo "cb=$cb $dt"; DEVO_BENCH_CB=$cb timeout 300 python bench.py --full --no-cpu-baseline --no-reference-api --no-f16 --dtype $dt --steps 100 --warmup 10 2>&1 | python -c "
 import sys, json
 for l in sys.stdin:
     if l.startswith('{'):

@@ -10,8 +10,8 @@ rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
 run_bench() {   # name, extra bench args
   local name=$1; shift
-  timeout 400 python "$R/bench.py" --no-cpu-baseline --no-f16 "$@" > "$O/${name}_bench.json" 2> "$O/${name}_bench.err"
-  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${name}_trace" -o k -- python "$R/bench.py" --no-cpu-baseline --no-f16 --steps 50 --warmup 5 "$@" > /dev/null 2> "$O/${name}_trace.log"
+  timeout 400 python "$R/bench.py" --full --no-cpu-baseline --no-f16 "$@" > "$O/${name}_bench.json" 2> "$O/${name}_bench.err"
+  timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/${name}_trace" -o k -- python "$R/bench.py" --full --no-cpu-baseline --no-f16 --steps 50 --warmup 5 "$@" > /dev/null 2> "$O/${name}_trace.log"
   python "$R/tools/rocprof_summary.py" "$O/${name}_trace" > "$O/${name}_kernel_trace.txt" 2>&1
 }
 run_pmc() {     # name, extra profile_corr args

@@ -7,7 +7,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 O=$R/gpurun_out/$TAG
 rm -rf "$O"; mkdir -p "$O"
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o k -- python "$R/bench.py" --steps 100 --warmup 10 --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/trace.log"
+timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/trace" -o k -- python "$R/bench.py" --full --steps 100 --warmup 10 --no-cpu-baseline > "$O/bench_under_rocprof.json" 2> "$O/trace.log"
 i=0
 for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" \
          "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
@@ -18,5 +18,5 @@ for C in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum" \
 done
 python "$R/tools/rocprof_summary.py" "$O/trace" > "$O/kernel_trace_summary.txt" 2>&1
 python "$R/tools/rocprof_summary.py" "$O" corr_fwd 2>&1 | grep -v "kernel_trace.csv" > "$O/pmc_corr_fwd_summary.txt"
-python "$R/bench.py" > "$O/bench.json" 2> "$O/bench.err"
+python "$R/bench.py" --full > "$O/bench.json" 2> "$O/bench.err"
 tail -1 "$O/bench.json"
