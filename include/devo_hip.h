@@ -27,9 +27,10 @@ typedef void* devo_stream_t; /* hipStream_t */
 enum { DEVO_OK = 0, DEVO_ERR_ARG = 1, DEVO_ERR_LAUNCH = 2, DEVO_ERR_UNSUPPORTED = 3, DEVO_ERR_WORKSPACE = 4 };
 enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
 
-#define DEVO_ABI_VERSION 5 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
+#define DEVO_ABI_VERSION 6 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
                               (devo_corr_pyramid_split_frames, devo_corr_patch_transpose_range), devo_stream_capturing; 4: devo_ba_table_offsets, devo_upd_graph_tables; 5: devo_ba_forward_prepared_delta_plan, devo_ba_import_tables, devo_upd_rs_corr_f16_net32,
                               devo_upd_rs_gru_f16_out32, devo_instnorm_cl, devo_instnorm_bias_cl, devo_bias_act_cl;
+                              6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -597,6 +598,31 @@ int devo_voxelize(const float* xs, const float* ys, const double* ts, const sign
  * is changed if any segment has no non-zero entry.  ws: devo_voxel_std_workspace_bytes(nseg). */
 size_t devo_voxel_std_workspace_bytes(int nseg);
 int devo_voxel_std(float* vox, int nseg, int64_t len, void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* The event front end of the loaders (utils/load_utils.py:47-76: EventSlicer.get_events -> rectify_map[y, x] -> to_voxel_grid
+ * -> trafos) for S windows of ONE stream in one call.  Events: ts ascending, f64 (ts_i64 = 0) or int64 microseconds (ts_i64 = 1);
+ * p i8 with 0 meaning -1.  Window s holds the events with t0[s] <= t < t1[s] (EventSlicer's rule; t0, t1 f64 device arrays
+ * of S) and is voxelised into out[s] (f32 [S, bins, H, W], zeroed here) with its time axis normalised by its own first and
+ * last event.  rectify_map f32 [H, W, 2] or NULL: when given, xs / ys are raw int32 sensor coordinates and the event votes
+ * at map[y, x] (an event outside the sensor is dropped); when NULL, xs / ys are f32 coordinates.  counts (int64 [S], may be
+ * NULL) receives every window's event count.  The window bounds are found on the device: no host synchronisation.
+ * ws: devo_voxelize_windows_workspace_bytes(S). */
+size_t devo_voxelize_windows_workspace_bytes(int S);
+int devo_voxelize_windows(const void* xs, const void* ys, const void* ts, int ts_i64, const signed char* ps, int64_t N, const double* t0,
+                          const double* t1, int S, const float* rectify_map, int H, int W, int bins, float* out, int64_t* counts, void* ws,
+                          size_t ws_bytes, devo_stream_t stream);
+
+/* RemoveHotPixelsVoxel(num_stds) (utils/event_utils.py:235-262), in place: vox f32 [nseg, len]; per segment the mean and the
+ * unbiased std of ALL len entries (fp64), then every entry with |v| > mean + num_stds * std is set to 0.
+ * ws: devo_voxel_hot_pixels_workspace_bytes(nseg). */
+size_t devo_voxel_hot_pixels_workspace_bytes(int nseg);
+int devo_voxel_hot_pixels(float* vox, int nseg, int64_t len, double num_stds, void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* rescale (utils/voxel_utils.py:31-51): out = vox with positive entries divided by the largest positive entry and negative
+ * entries divided by minus the smallest negative entry, both over all n entries; a sign with no entry is left unchanged.
+ * out may equal vox.  ws: devo_voxel_rescale_workspace_bytes(). */
+size_t devo_voxel_rescale_workspace_bytes(void);
+int devo_voxel_rescale(const float* vox, float* out, int64_t n, void* ws, size_t ws_bytes, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
