@@ -19,7 +19,10 @@
 //   * k_rescale_range / k_rescale_apply: voxel_utils.py:31-51 — positives divided by the maximum of ALL positives, negatives
 //     by minus the minimum of ALL negatives (both global over the tensor, as the reference's 1-D masked selection makes
 //     them); a polarity without entries is left as it is.
+//   * k_aug_gray_sum / k_aug_apply / k_aug_std: voxel_augment (voxel_utils.py:55-136) — [rescale on the fly], quantise to uint8 R / B
+//     images, one torchvision op, back to float, std from exact integer statistics; compiled without FMA contraction.
 #include <algorithm>
+#include <cmath>
 #include "common.h"
 
 namespace devo {
@@ -209,9 +212,13 @@ __global__ __launch_bounds__(256) void k_rescale_range(const float* __restrict__
   }
 #pragma unroll
   for (int off = 32; off >= 1; off >>= 1) { pmax = fmaxf(pmax, __shfl_xor(pmax, off)); nmax = fmaxf(nmax, __shfl_xor(nmax, off)); }
-  if ((threadIdx.x & 63) == 0) {
-    if (pmax > 0.0f) atomicMax(mx, __float_as_uint(pmax));
-    if (nmax > 0.0f) atomicMax(mx + 1, __float_as_uint(nmax));
+  // one atomic per workgroup and sign: same-address atomics serialise in L2, one per wave cost ~0.1 ms over 92 MB
+  __shared__ float s_red[2][4];
+  if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = pmax; s_red[1][threadIdx.x >> 6] = nmax; }
+  __syncthreads();
+  if (threadIdx.x < 2) {
+    const float m = fmaxf(fmaxf(s_red[threadIdx.x][0], s_red[threadIdx.x][1]), fmaxf(s_red[threadIdx.x][2], s_red[threadIdx.x][3]));
+    if (m > 0.0f) atomicMax(mx + threadIdx.x, __float_as_uint(m));
   }
 }
 
@@ -220,6 +227,234 @@ __global__ __launch_bounds__(256) void k_rescale_apply(const float* __restrict__
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
     const float a = v[i];
     out[i] = (a > 0.0f) ? a / pmax : (a < 0.0f) ? a / nmax : a;             // a / -vx_min: the negation is exact
+  }
+}
+
+// ---- voxel augmentation (voxel_utils.py:55-136: rescale -> evs2rgb -> uint8 -> one torchvision 0.13 uint8 tensor op -> float ->
+// rgb2evs -> std).  One image is one (segment, bin) slice with channels R = negative part, G = 0, B = positive part.  Every value
+// is formed in the reference's order with single fp32 roundings: hipcc contracts a*b + c into an FMA by default, and one FMA moves
+// a uint8 truncation boundary, so nothing below may be contracted.
+#pragma clang fp contract(off)
+
+enum { AUG_BRIGHTNESS = 0, AUG_CONTRAST, AUG_INVERT, AUG_POSTERIZE, AUG_SATURATION, AUG_SHARPNESS, AUG_SOLARIZE, AUG_NUM_OPS };
+
+struct AugArgs {
+  int op, nimg, H, W, rescale;
+  float r, omr;                 // _blend: ratio (an fp32 table value) and (float)(1.0 - ratio) formed in double
+  int mask, thr;                // posterize: q & mask; solarize: q >= thr (the threshold rounded up: q is an integer)
+};
+
+// (x).to(torch.uint8) of a value in [0, 255] (truncation); clamped first, as _blend does, so no input is undefined behaviour
+__device__ __forceinline__ int to_u8(float x) { return (int)fminf(fmaxf(x, 0.0f), 255.0f); }
+
+// [rescale] -> evs2rgb -> (255 * rgb).to(uint8) of one voxel: R = negative part, B = positive part (G is 0)
+__device__ __forceinline__ void quantise(float a, bool rescale, float pmax, float nmax, int& R, int& B) {
+  if (rescale) a = (a > 0.0f) ? a / pmax : (a < 0.0f) ? a / nmax : a;
+  R = (a < 0.0f) ? to_u8(255.0f * -a) : 0;
+  B = (a > 0.0f) ? to_u8(255.0f * a) : 0;
+}
+
+// rgb_to_grayscale: (0.2989 * r + 0.587 * g + 0.114 * b).to(uint8), three fp32 products and two fp32 adds, g = 0
+__device__ __forceinline__ int gray_u8(int R, int B) {
+  float l = 0.2989f * (float)R;
+  l = l + 0.587f * 0.0f;
+  l = l + 0.114f * (float)B;
+  return to_u8(l);
+}
+
+// _blend: (ratio * img1 + (1.0 - ratio) * img2).clamp(0, 255).to(uint8)
+__device__ __forceinline__ int blend_u8(int q, float img2, float r, float omr) {
+  float v = r * (float)q;
+  v = v + omr * img2;
+  return to_u8(v);
+}
+
+// one channel value q through the op; `other` is the contrast mean, the saturation grayscale or the sharpness blur
+__device__ __forceinline__ int aug_u8(int q, const AugArgs& a, float other) {
+  switch (a.op) {
+    case AUG_BRIGHTNESS: return blend_u8(q, 0.0f, a.r, a.omr);
+    case AUG_CONTRAST:
+    case AUG_SATURATION:
+    case AUG_SHARPNESS: return blend_u8(q, other, a.r, a.omr);
+    case AUG_INVERT: return 255 - q;
+    case AUG_POSTERIZE: return q & a.mask;
+    default: return q >= a.thr ? 255 - q : q;                              // solarize
+  }
+}
+
+// _blurred_degenerate_image at an interior pixel: round(conv([[1,1,1],[1,5,1],[1,1,1]] / 13)).  k / 13 for an integer k is never
+// within 1/26 of a tie, far beyond the fp32 rounding of any summation order, so round(k / 13) = floor((2k + 13) / 26) exactly
+__device__ __forceinline__ int blur_u8(int sum9, int centre) { return (2 * (sum9 + 4 * centre) + 13) / 26; }
+
+template <bool VEC>
+__device__ __forceinline__ void load4(const float* __restrict__ row, int x0, int W, float v[4]) {
+  if (VEC) {
+    const float4 t = *reinterpret_cast<const float4*>(row + x0);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+  } else {
+#pragma unroll
+    for (int k = 0; k < 4; k++) v[k] = (x0 + k < W) ? row[x0 + k] : 0.0f;
+  }
+}
+
+// gsum[img] = sum over the image of its uint8 grayscale (adjust_contrast's mean, exact); `bpi` workgroups per image
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_aug_gray_sum(const float* __restrict__ vox, AugArgs a, int bpi, const unsigned* __restrict__ mx,
+                                                      unsigned long long* __restrict__ gsum) {
+  __shared__ unsigned long long s_red[4];
+  const int img = blockIdx.x / bpi, b = blockIdx.x - img * bpi;
+  const int64_t len = (int64_t)a.H * a.W;
+  const float* p = vox + (int64_t)img * len;
+  const float pmax = __uint_as_float(mx[0]), nmax = __uint_as_float(mx[1]);
+  unsigned long long s = 0;
+  for (int64_t i = ((int64_t)b * 256 + threadIdx.x) * 4; i < len; i += (int64_t)bpi * 256 * 4) {
+    float v[4];
+    load4<VEC>(p + i, 0, (int)(len - i < 4 ? len - i : 4), v);             // VEC: len is a multiple of 4
+    unsigned t = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      int R, B;
+      quantise(v[k], a.rescale, pmax, nmax, R, B);
+      t += (i + k < len) ? (unsigned)gray_u8(R, B) : 0u;
+    }
+    s += t;
+  }
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
+  if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(gsum + img, (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]));
+}
+
+// the op pass: every thread takes 4 neighbouring voxels of one row (a 16-byte load when VEC), quantises, applies the op, writes
+// B'/255 + (-(R'/255)) and, with `stats`, adds the segment's exact integer statistics of d = B' - R' (count of d != 0, sum d,
+// sum d^2) for the standardisation.  Sharpness reads the rows above and below from the caches.  `bps` workgroups per segment.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_aug_apply(const float* __restrict__ vox, float* __restrict__ out, AugArgs a, int bps,
+                                                   const unsigned* __restrict__ mx, const unsigned long long* __restrict__ gsum,
+                                                   unsigned long long* __restrict__ stats) {
+  __shared__ unsigned long long s_red[3][4];
+  const int seg = blockIdx.x / bps, b = blockIdx.x - seg * bps;
+  const int H = a.H, W = a.W, Wq = (W + 3) >> 2;
+  const int64_t per_img = (int64_t)H * Wq, groups = (int64_t)a.nimg * per_img, img_len = (int64_t)H * W;
+  const float pmax = __uint_as_float(mx[0]), nmax = __uint_as_float(mx[1]);
+  const bool sharp = a.op == AUG_SHARPNESS && H > 2 && W > 2;              // adjust_sharpness returns a 2-pixel image unchanged
+  const float fimg_len = (float)img_len;
+  unsigned long long cnt = 0, s1 = 0, s2 = 0;                               // s1: two's complement
+  for (int64_t g = (int64_t)b * 256 + threadIdx.x; g < groups; g += (int64_t)bps * 256) {
+    const int i = (int)(g / per_img);
+    const int64_t rem = g - (int64_t)i * per_img;
+    const int y = (int)(rem / Wq), x0 = (int)(rem - (int64_t)y * Wq) * 4;
+    const int64_t img = (int64_t)seg * a.nimg + i;
+    const float* src = vox + img * img_len;
+    float v[4];
+    load4<VEC>(src + (int64_t)y * W, x0, W, v);
+    int R[4], B[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) quantise(v[k], a.rescale, pmax, nmax, R[k], B[k]);
+    int Ro[4], Bo[4];
+    if (a.op != AUG_SHARPNESS) {
+      const float mean = (a.op == AUG_CONTRAST) ? (float)gsum[img] / fimg_len : 0.0f;   // torch.mean on CPU: sum / N
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const float other = (a.op == AUG_SATURATION) ? (float)gray_u8(R[k], B[k]) : mean;
+        Ro[k] = aug_u8(R[k], a, other);
+        Bo[k] = aug_u8(B[k], a, other);
+      }
+    } else if (!sharp) {
+#pragma unroll
+      for (int k = 0; k < 4; k++) { Ro[k] = R[k]; Bo[k] = B[k]; }
+    } else {
+      // blur of the interior pixels (1 <= x, y <= size - 2); border pixels blend with themselves (result = img.clone())
+      int bR[4], bB[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) { bR[k] = R[k]; bB[k] = B[k]; }
+      if (y >= 1 && y <= H - 2) {
+        int nR[3][6], nB[3][6];
+#pragma unroll
+        for (int dy = 0; dy < 3; dy++) {
+          const float* row = src + (int64_t)(y - 1 + dy) * W;
+          float w[4];
+          if (dy == 1) {
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = v[k];
+          } else {
+            load4<VEC>(row, x0, W, w);
+          }
+          const float left = (x0 > 0) ? row[x0 - 1] : 0.0f, right = (x0 + 4 < W) ? row[x0 + 4] : 0.0f;
+          quantise(left, a.rescale, pmax, nmax, nR[dy][0], nB[dy][0]);
+#pragma unroll
+          for (int k = 0; k < 4; k++) quantise(w[k], a.rescale, pmax, nmax, nR[dy][k + 1], nB[dy][k + 1]);
+          quantise(right, a.rescale, pmax, nmax, nR[dy][5], nB[dy][5]);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+          const int x = x0 + k;
+          if (x >= 1 && x <= W - 2) {
+            int sr = 0, sb = 0;
+#pragma unroll
+            for (int dy = 0; dy < 3; dy++)
+#pragma unroll
+              for (int dx = 0; dx < 3; dx++) { sr += nR[dy][k + dx]; sb += nB[dy][k + dx]; }
+            bR[k] = blur_u8(sr, R[k]);
+            bB[k] = blur_u8(sb, B[k]);
+          }
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        Ro[k] = aug_u8(R[k], a, (float)bR[k]);
+        Bo[k] = aug_u8(B[k], a, (float)bB[k]);
+      }
+    }
+    float o[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      o[k] = (float)Bo[k] / 255.0f + (-((float)Ro[k] / 255.0f));          // .to(float32) / 255, then rgb2evs: pos + (-neg)
+      const int d = Bo[k] - Ro[k];
+      if (x0 + k < W && d != 0) { cnt += 1; s1 += (unsigned long long)(long long)d; s2 += (unsigned long long)(d * d); }
+    }
+    float* dst = out + img * img_len + (int64_t)y * W;
+    if (VEC) {
+      *reinterpret_cast<float4*>(dst + x0) = make_float4(o[0], o[1], o[2], o[3]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; k++) if (x0 + k < W) dst[x0 + k] = o[k];
+    }
+  }
+  if (stats == nullptr) return;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) { cnt += __shfl_xor(cnt, off); s1 += __shfl_xor(s1, off); s2 += __shfl_xor(s2, off); }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  if (lane == 0) { s_red[0][wave] = cnt; s_red[1][wave] = s1; s_red[2][wave] = s2; }
+  __syncthreads();
+  if (threadIdx.x < 3) {
+    const unsigned long long t = (s_red[threadIdx.x][0] + s_red[threadIdx.x][1]) + (s_red[threadIdx.x][2] + s_red[threadIdx.x][3]);
+    atomicAdd(stats + 3 * seg + threadIdx.x, t);
+  }
+}
+
+// std(voxs) (sequence-wise) of the op pass's output in place, from its exact integer statistics: the outputs are d / 255, so
+// mean = sum d / (255 n) and E[v^2] = sum d^2 / (255^2 n); then v <- (v != 0) * (v - mean) / std as k_voxel_normalise.  Nothing
+// changes if a segment has no non-zero voxel (voxel_utils.py:19).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_aug_std(float* __restrict__ v, int64_t len, int nseg, int bps, const unsigned long long* __restrict__ stats) {
+  for (int s = 0; s < nseg; s++) if (stats[3 * s] == 0) return;
+  const int seg = blockIdx.x / bps, b = blockIdx.x - seg * bps;
+  const double cnt = (double)stats[3 * seg];
+  const float mean = (float)((double)(long long)stats[3 * seg + 1] / (255.0 * cnt));
+  const float ex2 = (float)((double)stats[3 * seg + 2] / (65025.0 * cnt));
+  const float sd = sqrtf(ex2 - mean * mean);
+  float* p = v + (int64_t)seg * len;
+  auto f = [&](float x) { return (x != 0.0f) ? (x - mean) / sd : 0.0f * ((x - mean) / sd); };
+  if (VEC) {
+    for (int64_t i = ((int64_t)b * 256 + threadIdx.x) * 4; i < len; i += (int64_t)bps * 256 * 4) {
+      float4 t = *reinterpret_cast<const float4*>(p + i);
+      t.x = f(t.x); t.y = f(t.y); t.z = f(t.z); t.w = f(t.w);
+      *reinterpret_cast<float4*>(p + i) = t;
+    }
+  } else {
+    for (int64_t i = (int64_t)b * 256 + threadIdx.x; i < len; i += (int64_t)bps * 256) p[i] = f(p[i]);
   }
 }
 
@@ -325,6 +560,64 @@ int devo_voxel_rescale(const float* vox, float* out, int64_t n, void* ws, size_t
   hipLaunchKernelGGL(k_rescale_range, dim3(nb), dim3(256), 0, st, vox, n, (unsigned*)ws);
   hipLaunchKernelGGL(k_rescale_apply, dim3(nb), dim3(256), 0, st, vox, out, n, (const unsigned*)ws);
   return check_launch("devo_voxel_rescale");
+}
+
+// [0, 8): rescale extremes (2 u32); then u64 grayscale sums [nseg * nimg]; then u64 {count, sum d, sum d^2} [nseg]
+size_t devo_voxel_augment_workspace_bytes(int nseg, int nimg) {
+  const size_t s = nseg > 0 ? (size_t)nseg : 1, i = nimg > 0 ? (size_t)nimg : 1;
+  return 8 + sizeof(unsigned long long) * (s * i + 3 * s);
+}
+
+int devo_voxel_augment(const float* vox, float* out, int nseg, int nimg, int H, int W, int rescale, int op, double factor, int standardise,
+                       void* ws, size_t ws_bytes, devo_stream_t stream) {
+  DEVO_REQUIRE(nseg >= 0 && nimg >= 0 && H > 0 && W > 0 && (int64_t)nseg * nimg <= INT32_MAX, "devo_voxel_augment: bad sizes");
+  DEVO_REQUIRE(op >= 0 && op < AUG_NUM_OPS, "devo_voxel_augment: unknown op %d", op);
+  const bool blend = op == AUG_BRIGHTNESS || op == AUG_CONTRAST || op == AUG_SATURATION || op == AUG_SHARPNESS;
+  DEVO_REQUIRE(!blend || (factor >= 0.0 && factor < 1e30), "devo_voxel_augment: the blend factor must be a finite non-negative number");
+  DEVO_REQUIRE(op != AUG_POSTERIZE || (factor >= 0.0 && factor <= 8.0 && factor == (double)(int)factor), "devo_voxel_augment: posterize bits must be an integer in [0, 8]");
+  DEVO_REQUIRE(op != AUG_SOLARIZE || (factor <= 255.0 && factor == factor), "devo_voxel_augment: the solarize threshold must be at most 255");
+  if (nseg == 0 || nimg == 0) return DEVO_OK;
+  DEVO_REQUIRE(vox != nullptr && out != nullptr && vox != out, "devo_voxel_augment: out must be a separate buffer");
+  if (ws == nullptr || ws_bytes < devo_voxel_augment_workspace_bytes(nseg, nimg)) { set_error("devo_voxel_augment: workspace too small"); return DEVO_ERR_WORKSPACE; }
+  hipStream_t st = (hipStream_t)stream;
+  int rc = zero_async(ws, devo_voxel_augment_workspace_bytes(nseg, nimg), st, "devo_voxel_augment (zero)");
+  if (rc != DEVO_OK) return rc;
+  unsigned* mx = (unsigned*)ws;
+  unsigned long long* gsum = (unsigned long long*)((char*)ws + 8);
+  unsigned long long* stats = gsum + (size_t)nseg * nimg;
+
+  AugArgs a;
+  a.op = op; a.nimg = nimg; a.H = H; a.W = W; a.rescale = rescale ? 1 : 0;
+  a.r = (float)factor;
+  a.omr = (float)(1.0 - factor);
+  a.mask = (op == AUG_POSTERIZE) ? ((0xFF << (8 - (int)factor)) & 0xFF) : 0xFF;
+  a.thr = (op == AUG_SOLARIZE) ? (int)std::max(std::ceil(factor), -1.0) : 0;
+
+  const int64_t img_len = (int64_t)H * W, n = (int64_t)nseg * nimg * img_len;
+  if (rescale) hipLaunchKernelGGL(k_rescale_range, dim3((unsigned)blocks_for(n, 256 * 8, 1024)), dim3(256), 0, st, vox, n, mx);
+  const bool vec = (W % 4 == 0) && ((uintptr_t)vox % 16 == 0) && ((uintptr_t)out % 16 == 0);
+  if (op == AUG_CONTRAST) {
+    const int nim = nseg * nimg;
+    const int bpi = std::min(blocks_for(img_len, 256 * 4 * 4, 256), std::max(INT32_MAX / nim, 1));
+    const dim3 grid((unsigned)((long long)nim * bpi)), block(256);
+    if (vec) hipLaunchKernelGGL(k_aug_gray_sum<true>, grid, block, 0, st, vox, a, bpi, (const unsigned*)mx, gsum);
+    else hipLaunchKernelGGL(k_aug_gray_sum<false>, grid, block, 0, st, vox, a, bpi, (const unsigned*)mx, gsum);
+  }
+  const int64_t groups = (int64_t)nimg * H * ((W + 3) / 4);
+  const int bps = std::min(blocks_for(groups, 256 * 2, 2048), std::max(4096 / nseg, 1));
+  const dim3 grid((unsigned)((long long)nseg * bps)), block(256);
+  unsigned long long* st_out = standardise ? stats : nullptr;
+  if (vec) hipLaunchKernelGGL(k_aug_apply<true>, grid, block, 0, st, vox, out, a, bps, (const unsigned*)mx, (const unsigned long long*)gsum, st_out);
+  else hipLaunchKernelGGL(k_aug_apply<false>, grid, block, 0, st, vox, out, a, bps, (const unsigned*)mx, (const unsigned long long*)gsum, st_out);
+  rc = check_launch("devo_voxel_augment");
+  if (rc != DEVO_OK || !standardise) return rc;
+  const int64_t len = (int64_t)nimg * img_len;
+  const bool vec_std = (len % 4 == 0) && ((uintptr_t)out % 16 == 0);
+  const int bps_std = std::min(blocks_for(len, 256 * 4 * 4, 2048), std::max(4096 / nseg, 1));
+  const dim3 grid_std((unsigned)((long long)nseg * bps_std));
+  if (vec_std) hipLaunchKernelGGL(k_aug_std<true>, grid_std, block, 0, st, out, len, nseg, bps_std, (const unsigned long long*)stats);
+  else hipLaunchKernelGGL(k_aug_std<false>, grid_std, block, 0, st, out, len, nseg, bps_std, (const unsigned long long*)stats);
+  return check_launch("devo_voxel_augment (std)");
 }
 
 }  // extern "C"

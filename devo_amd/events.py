@@ -1,7 +1,8 @@
 """Event stream -> voxel grid and voxel standardisation on the GPU, with the reference's function
 names and argument meaning: utils/event_utils.py:180-232 `to_voxel_grid`, utils/voxel_utils.py:6-28 `std`
 (== the NORM='std' branch of devo/devo.py:438-452), utils/voxel_utils.py:31-51 `rescale`, utils/event_utils.py:235-262
-`RemoveHotPixelsVoxel`; and the loaders' front end (utils/load_utils.py:47-76) for a whole recording: `voxel_grids` (many
+`RemoveHotPixelsVoxel`, utils/voxel_utils.py:55-136 `evs2rgb`, `rgb2evs`, `voxel_augment` (the training-time augmentation); and the
+loaders' front end (utils/load_utils.py:47-76) for a whole recording: `voxel_grids` (many
 windows of one stream in one call, rectified, hot pixels removed) and `real_data_voxels` (get_real_data_list's output).
 Inputs are device tensors; no CPU fallback."""
 import math
@@ -189,3 +190,102 @@ def real_data_voxels(xs, ys, ts, ps, tss_imgs_us, dT_ms, intrinsics, rectify_map
                 continue
             i = idx[c0 + j]
             yield grids[j], torch.as_tensor(intrinsics).clone(), (t0s[i] + t1s[i]) / 2
+
+
+# ---- voxel augmentation (utils/voxel_utils.py:55-136)
+
+AUG_OPS = ("adjust_brightness", "adjust_contrast", "invert", "posterize", "adjust_saturation", "adjust_sharpness", "solarize")   # :99-101, in order
+
+
+def evs2rgb(voxs):
+    """evs2rgb (utils/voxel_utils.py:55-67) without its host asserts: [..., h, w] -> [..., 3, h, w] with R = the negative part (as a
+    positive value), G = 0, B = the positive part."""
+    pos = torch.where(voxs < 0.0, torch.zeros_like(voxs), voxs)
+    neg = torch.where(voxs > 0.0, torch.zeros_like(voxs), voxs) * -1.0
+    return torch.stack((neg, torch.zeros_like(pos), pos), dim=-3)
+
+
+def rgb2evs(rgb):
+    """rgb2evs (utils/voxel_utils.py:70-75): [..., 3, h, w] -> B + (-R), [..., h, w]."""
+    return rgb[..., 2, :, :] + (-rgb[..., 0, :, :])
+
+
+def aug_factors(num_bins=10):
+    """_aug_factors (utils/voxel_utils.py:104-114): the factor table of every op in AUG_OPS order; `num_bins` is the number of factor
+    steps (not voxel bins).  float32 linspaces for the blends, the posterize bits (int32), a 0-d placeholder for invert, the solarize
+    thresholds (int32)."""
+    return [
+        torch.linspace(0.1, 0.2, num_bins),
+        torch.linspace(0.05, 0.2, num_bins),
+        torch.tensor(0.0),
+        8 - (torch.arange(num_bins) / ((num_bins - 1) / 4)).round().int(),
+        torch.linspace(0.05, 0.2, num_bins),
+        torch.linspace(0.9, 2.0, num_bins),
+        torch.linspace(0, 30, num_bins).round().int(),
+    ]
+
+
+def draw_augmentation(num_bins=10):
+    """voxel_augment's random choice (utils/voxel_utils.py:124-125): op = torch.randint(7, (1,)), then factor_index =
+    torch.randint(num_bins, (1,)), both from torch's default CPU generator and always both (invert draws an unused index too), so a
+    seeded run picks what the reference picks.  Host only.  Returns (op index into AUG_OPS, factor index)."""
+    op = int(torch.randint(len(AUG_OPS), (1,)).item())
+    factor_index = int(torch.randint(num_bins, (1,)).item())
+    return op, factor_index
+
+
+def _op_index(op):
+    if isinstance(op, str):
+        if op not in AUG_OPS:
+            raise ValueError(f"unknown augmentation op {op!r}: one of {AUG_OPS}")
+        return AUG_OPS.index(op)
+    i = int(op)
+    if not 0 <= i < len(AUG_OPS):
+        raise ValueError(f"unknown augmentation op index {i}: 0..{len(AUG_OPS) - 1}")
+    return i
+
+
+def _op_factor(op, factor_index, num_bins):
+    table = aug_factors(num_bins)[op]
+    if table.dim() == 0:
+        return 0.0                                                 # invert: no factor
+    if factor_index is None:
+        raise ValueError(f"{AUG_OPS[op]} needs a factor_index")
+    return float(table[int(factor_index)])                         # _blend's float(ratio): the fp32 table value
+
+
+def _augment_call(voxs, op, factor, rescale, standardise):
+    L.require_gpu(voxs)
+    if voxs.dim() != 5:
+        raise ValueError(f"expected voxel grids [b, n, c, h, w], got {tuple(voxs.shape)}")
+    b, n, c, h, w = voxs.shape
+    src = voxs.float().contiguous()
+    out = torch.empty_like(src)
+    lib = L.lib()
+    ws = torch.empty(lib.devo_voxel_augment_workspace_bytes(b, n * c), dtype=torch.uint8, device=voxs.device)
+    rc = lib.devo_voxel_augment(L.ptr(src), L.ptr(out), b, n * c, h, w, int(rescale), op, float(factor), int(standardise), L.ptr(ws),
+                                ws.numel(), L.stream())
+    L.check(rc, "events.voxel_augment")
+    return out
+
+
+def augment(voxs, op, factor_index=None, num_bins=10):
+    """_augment (utils/voxel_utils.py:78-96) with the op AUG_OPS[op] (an index or a name) at aug_factors(num_bins)[op][factor_index]
+    on an already rescaled grid voxs [b, n, c, h, w] (values in [-1, 1]; the reference asserts this, values outside are clamped here):
+    quantised to uint8 R / B images, the torchvision op applied per (b, n, c) image, back to float.  No standardisation.  Returns a new
+    float32 tensor."""
+    i = _op_index(op)
+    return _augment_call(voxs, i, _op_factor(i, factor_index, num_bins), rescale=False, standardise=False)
+
+
+def voxel_augment(voxs, rescaled=False, num_bins=10, op=None, factor_index=None):
+    """voxel_augment (utils/voxel_utils.py:117-136) of voxs [b, n, c, h, w]: rescale (unless `rescaled`), _augment with one op, then
+    std (sequence-wise), in one HIP call.  op=None draws op and factor index as the reference does (draw_augmentation: two draws from
+    torch's default CPU generator, no device synchronisation); otherwise op (index or name) and factor_index choose them.  Returns a new
+    float32 tensor and leaves voxs unchanged (the reference's rescale writes into its input)."""
+    if op is None:
+        if factor_index is not None:
+            raise ValueError("factor_index without op")
+        op, factor_index = draw_augmentation(num_bins)
+    i = _op_index(op)
+    return _augment_call(voxs, i, _op_factor(i, factor_index, num_bins), rescale=not rescaled, standardise=True)

@@ -11,6 +11,7 @@ projective_ops / altcorr / update / ba (HIP kernels + autograd) on synthetic Tar
 grids, the synthetic trajectory's poses and patch centres).  The module tree is the reference's (`update`, `patchify.fnet`,
 `patchify.inet`, `patchify.scorer`): the gradient bucket DDP all-reduces is the reference's by construction.
 """
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -23,18 +24,50 @@ FUSED_LOOKUP = __import__("os").environ.get("DEVO_TRAIN_FUSED_LOOKUP", "1") != "
 
 class TrainNet(nn.Module):
     """The parameters the reference's DDP wraps (eVONet, enet.py:218-233): `patchify` (fnet, inet, scorer — devo_amd.patchifier)
-    and `update` (devo_amd.update.Update), same names."""
+    and `update` (devo_amd.update.Update), same names.  `norm` and `randaug` are eVONet's (enet.py:218-233, train.py:381-382): how
+    the voxel grids are normalised before the patchifier, and whether training steps augment them (normalise_images)."""
 
-    def __init__(self, p=3, dim=384):
+    NORMS = ("none", "rescale", "norm", "standard", "std", "standard2", "std2")
+
+    def __init__(self, p=3, dim=384, norm="none", randaug=False):
         super().__init__()
+        if norm not in self.NORMS:
+            raise NotImplementedError(f"norm {norm!r} is not implemented: one of {self.NORMS}")
         from .update import Update
         from .patchifier import Patchifier
         self.patchify = Patchifier(patch_size=p, dim_inet=dim, dim_fnet=128, dim=32, patch_selector="scorer")
         self.update = Update(p, dim)
         self.P, self.dim = p, dim
+        self.norm, self.randaug = norm, randaug
 
     def num_parameters(self):
         return sum(q.numel() for q in self.parameters())
+
+    def normalise_images(self, images):
+        """enet.py:245-266: images [b, n, bins, h, w] normalised by `norm` (none, rescale / norm, standard / std: frame-wise std,
+        standard2 / std2: sequence-wise std); then, with `randaug` in training mode, on a third of the calls (np.random.rand() < 0.33)
+        events.voxel_augment (a random op and factor from torch's CPU generator), which like the reference raises for a norm that is
+        neither a rescale nor contains 'std'."""
+        from . import events
+        if self.norm == "none":
+            pass
+        elif self.norm in ("rescale", "norm"):
+            images = events.rescale(images)
+        elif self.norm in ("standard", "std"):
+            images = events.std(images, sequence=False)
+        elif self.norm in ("standard2", "std2"):
+            images = events.std(images)
+        else:
+            raise NotImplementedError(f"norm {self.norm!r} is not implemented")
+        if self.training and self.randaug:
+            if np.random.rand() < 0.33:
+                if self.norm in ("rescale", "norm"):
+                    images = events.voxel_augment(images, rescaled=True)
+                elif "std" in self.norm:
+                    images = events.voxel_augment(images, rescaled=False)
+                else:
+                    raise NotImplementedError(f"randaug with norm {self.norm!r} is not implemented")
+        return images
 
     def forward(self, batch, iters=18, corr_dropout=0.2, flow_weight=0.1, pose_weight=10.0):
         """One sequence (batch 1) through `iters` update iterations on its patch graph -> scalar loss
@@ -51,7 +84,7 @@ class TrainNet(nn.Module):
         E, n = ii.numel(), b["poses_gt"].shape[1]
         # enet.py:279-291: features, patch gathers and scores from the voxel grids; the patch centres are the synthetic
         # trajectory's (so that the ground-truth patches of the flow loss belong to them), the scorer is evaluated there
-        fmap, gmap, imap, _, _, scores = self.patchify(b["images"], b["M"], coords=b["centres"])
+        fmap, gmap, imap, _, _, scores = self.patchify(self.normalise_images(b["images"]), b["M"], coords=b["centres"])
         pyramid = [altcorr.channels_last(fmap), altcorr.channels_last(torch.nn.functional.avg_pool2d(fmap[0], 4, 4)[None])]   # enet.py:207-210
         imap = imap.view(1, -1, self.dim)
         Ps = SE3(b["poses_gt"])
@@ -125,10 +158,11 @@ def make_batch(workload="cfg2_m80", seed=1234, device="cuda"):
                 ii=d(ii), jj=d(jj), kk=d(kk), H=H, W=W, R=R, n=n, M=M, E=int(ii.numel()))
 
 
-def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None):
-    """net (DDP-wrapped when world_size > 1, train.py:106-107; ddp=True: also at world size 1, given a process group), AdamW (train.py:109)."""
+def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", randaug=False):
+    """net (DDP-wrapped when world_size > 1, train.py:106-107; ddp=True: also at world size 1, given a process group), AdamW (train.py:109).
+    norm, randaug: TrainNet's."""
     torch.manual_seed(seed)                                   # identical initial weights on every rank (train.py:41)
-    net = TrainNet().to(device).train()
+    net = TrainNet(norm=norm, randaug=randaug).to(device).train()
     model = net
     if world_size > 1 or ddp:
         from torch.nn.parallel import DistributedDataParallel as DDP

@@ -27,10 +27,11 @@ typedef void* devo_stream_t; /* hipStream_t */
 enum { DEVO_OK = 0, DEVO_ERR_ARG = 1, DEVO_ERR_LAUNCH = 2, DEVO_ERR_UNSUPPORTED = 3, DEVO_ERR_WORKSPACE = 4 };
 enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
 
-#define DEVO_ABI_VERSION 6 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
+#define DEVO_ABI_VERSION 7 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
                               (devo_corr_pyramid_split_frames, devo_corr_patch_transpose_range), devo_stream_capturing; 4: devo_ba_table_offsets, devo_upd_graph_tables; 5: devo_ba_forward_prepared_delta_plan, devo_ba_import_tables, devo_upd_rs_corr_f16_net32,
                               devo_upd_rs_gru_f16_out32, devo_instnorm_cl, devo_instnorm_bias_cl, devo_bias_act_cl;
                               6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
+                              7: devo_voxel_augment, devo_voxel_augment_workspace_bytes;
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -623,6 +624,18 @@ int devo_voxel_hot_pixels(float* vox, int nseg, int64_t len, double num_stds, vo
  * out may equal vox.  ws: devo_voxel_rescale_workspace_bytes(). */
 size_t devo_voxel_rescale_workspace_bytes(void);
 int devo_voxel_rescale(const float* vox, float* out, int64_t n, void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* voxel_augment / _augment (utils/voxel_utils.py:55-136) with torchvision 0.13's uint8 tensor ops: vox f32 [nseg, nimg, H, W]
+ * (a sequence of nimg = n * bins images) -> out f32, same shape, a separate buffer.  rescale != 0: vox is rescaled first (as
+ * devo_voxel_rescale, on the fly).  Every voxel becomes R = (uint8)(255 * max(-v, 0)), G = 0, B = (uint8)(255 * max(v, 0)), the op
+ * is applied per image, and out = B' / 255 - R' / 255.  op: 0 adjust_brightness, 1 adjust_contrast, 2 invert, 3 posterize,
+ * 4 adjust_saturation, 5 adjust_sharpness, 6 solarize; factor: the blend ratio (ops 0, 1, 4, 5), the bits (3), the threshold (6),
+ * unused (2).  standardise != 0: std(out) sequence-wise (devo_voxel_std's rule; nothing changes if a segment has no non-zero
+ * voxel), from exact integer statistics.  The result does not depend on the launch shape.  No host synchronisation; the
+ * workspace is cleared by a kernel (graph capture safe).  ws: devo_voxel_augment_workspace_bytes(nseg, nimg). */
+size_t devo_voxel_augment_workspace_bytes(int nseg, int nimg);
+int devo_voxel_augment(const float* vox, float* out, int nseg, int nimg, int H, int W, int rescale, int op, double factor, int standardise,
+                       void* ws, size_t ws_bytes, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
