@@ -27,11 +27,12 @@ typedef void* devo_stream_t; /* hipStream_t */
 enum { DEVO_OK = 0, DEVO_ERR_ARG = 1, DEVO_ERR_LAUNCH = 2, DEVO_ERR_UNSUPPORTED = 3, DEVO_ERR_WORKSPACE = 4 };
 enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
 
-#define DEVO_ABI_VERSION 7 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
+#define DEVO_ABI_VERSION 8 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
                               (devo_corr_pyramid_split_frames, devo_corr_patch_transpose_range), devo_stream_capturing; 4: devo_ba_table_offsets, devo_upd_graph_tables; 5: devo_ba_forward_prepared_delta_plan, devo_ba_import_tables, devo_upd_rs_corr_f16_net32,
                               devo_upd_rs_gru_f16_out32, devo_instnorm_cl, devo_instnorm_bias_cl, devo_bias_act_cl;
                               6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
                               7: devo_voxel_augment, devo_voxel_augment_workspace_bytes;
+                              8: devo_voxel_resample, devo_depth_normalise, devo_depth_normalise_workspace_bytes;
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -636,6 +637,29 @@ int devo_voxel_rescale(const float* vox, float* out, int64_t n, void* ws, size_t
 size_t devo_voxel_augment_workspace_bytes(int nseg, int nimg);
 int devo_voxel_augment(const float* vox, float* out, int nseg, int nimg, int H, int W, int rescale, int op, double factor, int standardise,
                        void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* The tail of a training sample (devo/data_readers/base.py:356-371): transform_rescale's resize and EVSDAugmentor's jitter, zoom and
+ * centre crop, then the depth normalisation.  ATen's CPU arithmetic (torch 2.10), FMAs where its build contracts and nowhere else.
+ * devo_voxel_resample: src f32 [B, C, H, W] -> dst f32 [B, C, Hc, Wc] (contiguous, separate buffers).  params: HOST int [B][4] =
+ * (Hs, Ws, y0, x0): sample b is resized to Hs x Ws (mode DEVO_RESAMPLE_BILINEAR: upsample_bilinear2d, align_corners=False, no
+ * explicit scale; DEVO_RESAMPLE_NEAREST: nearest_idx) and only rows y0 .. y0 + Hc - 1, columns x0 .. x0 + Wc - 1 of it are
+ * computed (0 <= y0, y0 + Hc <= Hs, likewise x).  Jitter v + ((u - 0.5) * 2) * 1e-4 on every source tap before interpolation:
+ * u = noise[same index as the tap] when noise (device, src's shape) is given, else, when seeds (HOST uint64 [B]) is given, a
+ * 24-bit uniform hashed from (seeds[b], the tap's index within sample b); neither: no jitter.  Samples go DEVO_RESAMPLE_MAX_BATCH
+ * to a launch, with their parameters as kernel arguments (nothing is copied to the device).  C * H * W < 2^32. */
+#define DEVO_RESAMPLE_MAX_BATCH 64
+enum { DEVO_RESAMPLE_BILINEAR = 0, DEVO_RESAMPLE_NEAREST = 1 };
+int devo_voxel_resample(const float* src, float* dst, int B, int C, int H, int W, int Hc, int Wc, const int* params, int mode, const float* noise,
+                        const uint64_t* seeds, devo_stream_t stream);
+
+/* The depth normalisation of __getitem__ for B samples of n disparities each (disps f32 [B, n], in place): s = factor *
+ * torch.quantile(disps[b], q) exactly as torch computes it for fp32 input (rank q * (n - 1) in fp32, the last index if a NaN is
+ * present, ATen's lerp; NaN sorts last), then disps[b] /= s, poses[b, p, 0:3] *= s for poses f32 [B, P, pose_stride] (may be NULL)
+ * and s_out[b] = s (may be NULL).  Exact radix select; no size limit below 2^31.  No host synchronisation; the workspace
+ * (devo_depth_normalise_workspace_bytes(B)) is cleared by a kernel (graph capture safe). */
+size_t devo_depth_normalise_workspace_bytes(int B);
+int devo_depth_normalise(float* disps, int64_t n, int B, float* poses, int P, int pose_stride, float q, float factor, float* s_out, void* ws,
+                         size_t ws_bytes, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
