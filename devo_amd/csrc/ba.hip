@@ -36,16 +36,11 @@ struct BaMeta { int n_seg; int fail; int sig; int pad; };   // sig: what the wor
 __host__ __device__ __forceinline__ int ba_sig(int E, int N) { return (int)(0x5ec0de00u ^ ((unsigned)E * 2654435761u) ^ ((unsigned)N << 24)); }
 
 // ------------------------------------------------------------------------------------------------- utilities
-// Sum over the 64 lanes, returned to every lane.  DEVO_BA_SHFL_SUM: the butterfly of rounds 1-5 (six ds_bpermute round trips through the LDS
-// crossbar per value); default (round 6): DPP adds on the vector ALU — the scan of corr_tile.h's wave_inclusive_sum (row_shr 1 / 2 / 4 / 8, row_bcast
-// 15 / 31), the total in lane 63, v_readlane.  All 64 lanes must be active (every caller's are).  The order of the additions differs from the
-// butterfly's: results move in the last bits, every kernel of this file uses the same form.
+// Sum over the 64 lanes, returned to every lane.  Round 6: DPP adds on the vector ALU — the scan of corr_tile.h's wave_inclusive_sum (row_shr
+// 1 / 2 / 4 / 8, row_bcast 15 / 31), the total in lane 63, v_readlane — where rounds 1-5 used a butterfly (six ds_bpermute round trips through the
+// LDS crossbar per value).  All 64 lanes must be active (every caller's are).  The order of the additions differs from the butterfly's: results
+// moved in the last bits, every kernel of this file uses the same form.
 __device__ __forceinline__ float wave_sum(float v) {
-#ifdef DEVO_BA_SHFL_SUM
-#pragma unroll
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off);
-  return v;
-#else
   auto dpp = [](float x, auto ctrl, auto rows) { return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, decltype(rows)::value, 0xf, false)); };
   v += dpp(v, std::integral_constant<int, 0x111>{}, std::integral_constant<int, 0xf>{});
   v += dpp(v, std::integral_constant<int, 0x112>{}, std::integral_constant<int, 0xf>{});
@@ -54,7 +49,6 @@ __device__ __forceinline__ float wave_sum(float v) {
   v += dpp(v, std::integral_constant<int, 0x142>{}, std::integral_constant<int, 0xa>{});
   v += dpp(v, std::integral_constant<int, 0x143>{}, std::integral_constant<int, 0xc>{});
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), 63));
-#endif
 }
 __device__ __forceinline__ unsigned wave_or(unsigned v) {
 #pragma unroll
@@ -319,13 +313,6 @@ __global__ __launch_bounds__(256) void k_prep_clear2(int4* __restrict__ a0, int4
 // patches — DEVO's sliding window is ~2k patches); otherwise the same arrays in the workspace are used.
 constexpr int PREP_FLAGS_LDS = 16384;
 constexpr int PREP_SEGS_LDS = 8192;
-#ifdef DEVO_PREP_TRACE
-// debug build (tools/build_variant.sh preptrace ba -DDEVO_PREP_TRACE; tools/bench_prepare.py): 100 MHz stamps of thread 0 at the phase boundaries
-__device__ unsigned long long g_prep_trace[16];
-#define PREP_STAMP(i) do { __syncthreads(); if (threadIdx.x == 0) g_prep_trace[i] = wall_clock64(); } while (0)
-#else
-#define PREP_STAMP(i) do { } while (0)
-#endif
 template <int CACHE>      // CACHE = 0: kk is re-read by every pass; else ceil(E / 1024) <= CACHE edges per thread in registers
 __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, int E, int Np, int max_seg, BaMeta* meta,
                                                 int* g_rank, int* g_counts, int* g_cursor, int* ku, int* kx, int* perm_a,
@@ -338,7 +325,6 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
   __shared__ int s_min, s_max;
   const int t = threadIdx.x;
   if (t == 0) { s_min = 0x7fffffff; s_max = -1; }
-  PREP_STAMP(0);
   // patch id of edge t + 1024 i (or -1: out of range / no edge).  CACHED: all loads in flight at once, every later
   // pass runs from registers; otherwise kk is re-read by every pass.
   constexpr bool CACHED = CACHE > 0;
@@ -428,7 +414,6 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
     for (int i = n_seg + t; i <= max_seg; i += 1024) g_counts[i] = E;      // segment n_seg starts at E; empty tails
     return;
   }
-  PREP_STAMP(1);                                               // kk loaded, ascending test done
   int lo = 0x7fffffff, hi = -1;
 #pragma unroll
   for (int i = 0; i < iters; i++) { const int k = patch_of(i); if (k >= 0) { lo = min(lo, k); hi = max(hi, k); } }
@@ -443,9 +428,7 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
 #pragma unroll
   for (int i = 0; i < iters; i++) { const int k = patch_of(i); if (k >= 0) rank[k - kmin] = 1; }
   __syncthreads();
-  PREP_STAMP(2);                                               // range, flags
   const int n_seg = block_excl_scan_1024(rank, Rg, s_part);
-  PREP_STAMP(3);                                               // unique ids ranked
   // (sig: the workspace holds a prepared graph once this kernel is through — the in-segment order is restored below)
   if (t == 0) { meta->n_seg = n_seg; meta->fail = 0; meta->pad = ascending; meta->sig = sig; }
   int* counts = (n_seg <= PREP_SEGS_LDS) ? s_counts : g_counts;
@@ -507,12 +490,10 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
       if (r >= 0 && hl == lane) atomicAdd(&counts[r], nh - lane);
     }
   }
-  PREP_STAMP(4);                                               // segments counted
   for (int p = t; p < Rg; p += 1024)
     if (rank[p + 1] != rank[p]) kx[rank[p]] = kmin + p;
   __syncthreads();
   block_excl_scan_1024(counts, n_seg, s_part);
-  PREP_STAMP(5);                                               // segment starts
 #pragma unroll
   for (int i = 0; i < iters; i++) {
     const int e = t + 1024 * i;
@@ -529,10 +510,8 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
       if (sgm >= 0) perm_a[counts[sgm] + base + (lane - hl)] = e;
     }
   }
-  PREP_STAMP(6);                                               // scattered
   // publish the segment starts: entries beyond n_seg = E so that any reader sees empty tails
   for (int i = t; i <= max_seg; i += 1024) g_counts[i] = (i <= n_seg) ? counts[i] : E;
-  PREP_STAMP(7);                                               // starts published
   // restore a deterministic (ascending edge id) order inside every segment: rank sort, one wave per segment (the work of
   // k_sort_segments, which the multi-kernel path for huge edge lists still launches)
   __threadfence_block();
@@ -586,7 +565,6 @@ __device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, 
       }
     }
   }
-  PREP_STAMP(8);                                               // segments sorted
 }
 
 template <int CACHE>
@@ -904,37 +882,19 @@ __global__ __launch_bounds__(ACC_THREADS) void k_ba_accumulate_t(
   }
 }
 
-// Register-resident accumulate kernel for N <= NMAX optimised poses (the DEVO sizes: 7..14).
-// Each wave keeps its OWN copy of the lower block-triangle of S in registers: lane (a,b) = (lane/6, lane%6) < 36
-// holds entry [a][b] of every 6x6 block, Sreg[block].  A regular patch (<= 64 edges, one source frame, distinct
-// target frames) is folded in with wave-uniform control flow and plain LDS reads of a per-wave scratch that the
-// patch's edge lanes filled: no atomics, fixed summation order.  Irregular patches take the atomic path into the
-// workgroup's LDS system.  At the end the register copies are added into LDS one wave at a time.
-#ifdef DEVO_ACC_TRACE
-// debug build (tools/build_variant.sh acctrace ba -DDEVO_ACC_TRACE; tools/acc_trace.py): 100 MHz time stamps of every wave of the
-// last k_ba_accumulate_reg launch
-__device__ unsigned long long g_acc_trace[256 * 8 * 16];
-#define ACC_STAMP(i) do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); \
-    if (lane == 0 && blockIdx.x < 256) g_acc_trace[(blockIdx.x * 8 + wave) * 16 + (i)] = wall_clock64(); } while (0)
-#define ACC_STAMP_FIRST(i) do { if (half == 0) ACC_STAMP(i); } while (0)      // the wave's first patch only
-#define ACC_STAMP_PATCH(i) ACC_STAMP((i) + 2 * half)
-#else
-#define ACC_STAMP(i) do { } while (0)
-#define ACC_STAMP_FIRST(i) do { } while (0)
-#define ACC_STAMP_PATCH(i) do { } while (0)
-#endif
-constexpr int REG_WAVES = 4;      // register fold: 256 threads, one wave per SIMD, so the register copy of S never spills
+// Register-path accumulate kernel for N <= NMAX optimised poses (the DEVO sizes: 7..14).
+// Each wave keeps its OWN copy of the lower block-triangle of S: lane (a,b) = (lane/6, lane%6) < 36 holds entry [a][b]
+// of every 6x6 block.  A regular patch (<= 64 edges, one source frame, distinct target frames) is folded in with
+// wave-uniform control flow and plain LDS reads of a per-wave scratch that the patch's edge lanes filled: no atomics,
+// fixed summation order.  Irregular patches take the atomic path into the workgroup's LDS system.  At the end the
+// workgroup adds the wave copies and that system.
 constexpr int SCR_ROWS = 28;     // per-edge scratch rows: Jj_x[6] Jj_y[6] Ji_x[6] Ji_y[6] w_x w_y (w r)_x (w r)_y
-// Where a wave keeps its copy of the block triangle.
-//  LDSFOLD = false: in registers (105 accumulators per lane at N = 14: 256 VGPRs + 153 AGPRs, ONE wave per SIMD, WAVES = 4).  The
-//    fold is instruction-issue bound with nothing to interleave (profiles/README.md, r02c), and cfg2's 1440 patches meet 1024 waves:
-//    the kernel lasts two patches.
-//  LDSFOLD = true: in the wave's own LDS slab (the layout of the compact partial).  The first patch of a wave STORES its blocks (no
-//    zero-fill, no read), later ones read-modify-write; nothing is parked at the end.  ~150 registers: two waves per SIMD, WAVES =
-//    8 / 6 / 4 for N <= 11 / 14 / 16 by the LDS the slabs need — at cfg2 every wave has ONE patch.  Same sums in the same order per
-//    wave; the workgroup adds the slabs in wave order: deterministic like the register form.
-__host__ __device__ constexpr int scr_ld(bool ldsfold) { return ldsfold ? 48 : 64; }   // slots per scratch row (a regular patch has <= that many edges)
-
+constexpr int SCR_LD = 48;       // slots per scratch row (a regular patch has <= that many edges)
+// A wave keeps its copy of the block triangle in its own LDS slab (LDSFOLD; the layout of the compact partial).  The first patch of a wave
+// STORES its blocks (no zero-fill, no read), later ones read-modify-write.  ~150 registers: two waves per SIMD, WAVES = 8 / 6 / 4 for
+// N <= 11 / 14 / 16 by the LDS the slabs need — at cfg2 every wave has ONE patch.  Same sums in the same order per wave; the workgroup
+// adds the slabs in wave order: deterministic.  (The register fold of rounds 2-5 — 105 accumulators per lane at N = 14, one wave per SIMD,
+// instruction-issue bound: profiles/README.md, r02c — is in git history.)
 template <int NMAX, int WAVES, bool LDSFOLD>
 __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
     const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ intr,
@@ -942,7 +902,8 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const int64_t* __restrict__ kk,
     const int* __restrict__ perm, const int* __restrict__ seg_start, BaMeta* __restrict__ meta, int P, int t0,
     int N, float* __restrict__ partials, float* __restrict__ patch_rec, float* __restrict__ patch_col, int iter, int sig, int max_seg) {
-  constexpr int REG_WAVES = WAVES, REG_THREADS = WAVES * 64, SLD = scr_ld(LDSFOLD);
+  static_assert(LDSFOLD, "the block triangle is folded in LDS");
+  constexpr int REG_WAVES = WAVES, REG_THREADS = WAVES * 64, SLD = SCR_LD;
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const int n6 = 6 * N, LD = n6 + 1;
   float* S_lds = smem;
@@ -950,7 +911,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
   float* col_all = y_lds + n6;
   float* scr_all = col_all + REG_WAVES * n6;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  ACC_STAMP(0);
   float* col = col_all + wave * n6;
   float* scr = scr_all + wave * (SCR_ROWS * SLD);
   __shared__ int s_used_atomic;                                 // did any wave of this workgroup take the atomic path?
@@ -965,16 +925,11 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
   AccCtx K{poses, patches, target, weight, ii, jj, kk, perm, patch_rec, patch_col, intr[0], intr[1], intr[2], intr[3], lmbda[0],
            P, t0, N, n6, LD};
 
-  ACC_STAMP(1);
   const int pa = (lane < 36) ? lane / 6 : 0, pb = (lane < 36) ? lane % 6 : 0;    // this lane's position inside a 6x6 block
-  float Sreg[LDSFOLD ? 1 : NMAX * (NMAX + 1) / 2];
-#pragma unroll
-  for (int i = 0; i < (LDSFOLD ? 1 : NMAX * (NMAX + 1) / 2); i++) Sreg[i] = 0.0f;
-  float yreg[2] = {0.0f, 0.0f};                                 // rows lane, lane + 64  (n6 <= 96)
   const int nt = tri_blocks(N) * 36;
   float* tri_all = scr_all + REG_WAVES * (SCR_ROWS * SLD);     // [REG_WAVES][nt + n6]
-  float* tri = tri_all + wave * (nt + n6);                     // this wave's compact copy (LDSFOLD) / parking slab
-  bool fresh = true;                                           // LDSFOLD: nothing in the slab yet — the first patch stores
+  float* tri = tri_all + wave * (nt + n6);                     // this wave's compact copy
+  bool fresh = true;                                           // nothing in the slab yet — the first patch stores
 
   // a workspace that was not prepared for this (E, N) is not touched: the call fails (status -1) instead of walking
   // garbage tables; a prepared graph may be solved many times (the sticky failure flag is reset here)
@@ -984,14 +939,10 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
                                                                // dependent round trip less in front of the edge terms)
   if (iter == 0 && blockIdx.x == 0 && tid == 0) meta->fail = prepared ? 0 : -1;
   for (int s = blockIdx.x * REG_WAVES + wave; s < n_seg; s += gridDim.x * REG_WAVES) {
-#ifdef DEVO_ACC_TRACE
-    const int half = (s >= gridDim.x * REG_WAVES) ? 1 : 0;      // the wave's first / a later patch
-#endif
     const int a0 = seg_start[s], m = seg_start[s + 1] - a0;
     if (m > 64) { if (lane == 0) s_used_atomic = 1; accumulate_segment_atomic(K, s, a0, m, S_lds, y_lds, col, lane); continue; }
     const bool act = lane < m;
     const int e = act ? (ident ? a0 + lane : perm[a0 + lane]) : 0;
-    ACC_STAMP_FIRST(2);
     EdgeTerms T;
     int ix = -1, jx = -1;
     if (act) {
@@ -1005,7 +956,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
 #pragma unroll
       for (int c = 0; c < 6; c++) { T.Ji[0][c] = T.Ji[1][c] = T.Jj[0][c] = T.Jj[1][c] = 0.0f; }
     }
-    ACC_STAMP_PATCH(3);
     // ---- regular?  one source frame, distinct target frames (frame -> lane table built through the column buffer)
     const unsigned long long bi = __ballot(ix >= 0);
     const int src = bi ? __shfl(ix, __ffsll((long long)bi) - 1) : -1;
@@ -1027,7 +977,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
       continue;
     }
     const int slot = (jx >= 0) ? jx : N + __popcll(fixm & ((1ULL << lane) - 1ULL));
-    ACC_STAMP_FIRST(8);
 
     // ---- per-edge quantities into the wave's scratch [row][slot]; the patch's E column into `col`
     for (int i = lane; i < n6; i += 64) col[i] = 0.0f;
@@ -1074,8 +1023,7 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
     if (N == 0) continue;
     for (int i = lane; i < n6; i += 64) patch_col[(int64_t)s * n6 + i] = col[i];  // the patch's E column, for the retraction
 
-    ACC_STAMP_FIRST(9);
-    // ---- fold the patch into the register-resident block triangle.  Everything a lane needs is pulled into registers
+    // ---- fold the patch into the wave's block triangle.  Everything a lane needs is pulled into registers
     //      with wide LDS reads first (frame slots 0..NSL-1: element [pa] / [pb] of every Jacobian row), then the 6x6 block
     //      entries are pure register arithmetic with no branches; slots without an edge hold zeros, block rows >= N are
     //      computed but never flushed.
@@ -1105,41 +1053,31 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
           if (fr == fc) v += Dg[fr];
           return v;
         };
-        if constexpr (LDSFOLD) {
-          // the slab has tri_blocks(N) blocks (fr < N: wave-uniform).  First patch of the wave: stores only; later ones: a block
-          // row's old values are fetched together (one LDS latency per row, not per block), then added and stored
-          float* tp = tri + lane;
-          if (lane < 36) {
-            if (fresh) {
-              int blk = 0;
+        // the slab has tri_blocks(N) blocks (fr < N: wave-uniform).  First patch of the wave: stores only; later ones: a block
+        // row's old values are fetched together (one LDS latency per row, not per block), then added and stored
+        float* tp = tri + lane;
+        if (lane < 36) {
+          if (fresh) {
+            int blk = 0;
 #pragma unroll
-              for (int fr = 0; fr < NMAX; fr++) {
+            for (int fr = 0; fr < NMAX; fr++) {
 #pragma unroll
-                for (int fc = 0; fc <= fr; fc++, blk++) if (fr < N) tp[blk * 36] = block_value(fr, fc);
-              }
-            } else {
+              for (int fc = 0; fc <= fr; fc++, blk++) if (fr < N) tp[blk * 36] = block_value(fr, fc);
+            }
+          } else {
 #pragma unroll
-              for (int fr = 0; fr < NMAX; fr++) {
-                if (fr < N) {
-                  float old[NMAX];
+            for (int fr = 0; fr < NMAX; fr++) {
+              if (fr < N) {
+                float old[NMAX];
 #pragma unroll
-                  for (int fc = 0; fc <= fr; fc++) old[fc] = tp[(fr * (fr + 1) / 2 + fc) * 36];
+                for (int fc = 0; fc <= fr; fc++) old[fc] = tp[(fr * (fr + 1) / 2 + fc) * 36];
 #pragma unroll
-                  for (int fc = 0; fc <= fr; fc++) tp[(fr * (fr + 1) / 2 + fc) * 36] = old[fc] + block_value(fr, fc);
-                }
+                for (int fc = 0; fc <= fr; fc++) tp[(fr * (fr + 1) / 2 + fc) * 36] = old[fc] + block_value(fr, fc);
               }
             }
           }
-        } else {
-          int blk = 0;
-#pragma unroll
-          for (int fr = 0; fr < NMAX; fr++) {
-#pragma unroll
-            for (int fc = 0; fc <= fr; fc++, blk++) Sreg[blk] += block_value(fr, fc);
-          }
         }
       }
-      ACC_STAMP_FIRST(10);
       if (src >= 0) {
         // pass 2 (source frame optimised): row and column `src` get the (i,j) / (j,i) blocks, the diagonal gets B_ii;
         // a self edge (target == source) puts B_ij + B_ji on the diagonal as well
@@ -1162,31 +1100,17 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
         for (int q = NSL; q < nslot; q++)                        // more fixed-target edges than spare slots (rare)
           bii += scr[24 * SLD + q] * scr[(12 + pa) * SLD + q] * scr[(12 + pb) * SLD + q] +
                  scr[25 * SLD + q] * scr[(18 + pa) * SLD + q] * scr[(18 + pb) * SLD + q];
-        if constexpr (LDSFOLD) {
-          // the N blocks of row / column `src` of the slab, after pass 1's stores to the same addresses (LDS is in order)
+        // the N blocks of row / column `src` of the slab, after pass 1's stores to the same addresses (LDS is in order)
 #pragma unroll
-          for (int f = 0; f < NMAX; f++) {
-            if (f < N && lane < 36) {
-              const int blk = (f < src) ? src * (src + 1) / 2 + f : f * (f + 1) / 2 + src;          // wave-uniform
-              const float d = (f < src) ? -Cq[f] : (f > src) ? -Rr[f] : bii - (Rr[f] + Cq[f]);
-              tri[blk * 36 + lane] += d;
-            }
-          }
-        } else {
-#pragma unroll
-          for (int sf = 0; sf < NMAX; sf++) {
-            if (src == sf) {                                       // wave-uniform
-#pragma unroll
-              for (int fc = 0; fc < sf; fc++) Sreg[sf * (sf + 1) / 2 + fc] -= Cq[fc];
-#pragma unroll
-              for (int fr = sf + 1; fr < NMAX; fr++) Sreg[fr * (fr + 1) / 2 + sf] -= Rr[fr];
-              Sreg[sf * (sf + 1) / 2 + sf] += bii - (Rr[sf] + Cq[sf]);
-            }
+        for (int f = 0; f < NMAX; f++) {
+          if (f < N && lane < 36) {
+            const int blk = (f < src) ? src * (src + 1) / 2 + f : f * (f + 1) / 2 + src;          // wave-uniform
+            const float d = (f < src) ? -Cq[f] : (f > src) ? -Rr[f] : bii - (Rr[f] + Cq[f]);
+            tri[blk * 36 + lane] += d;
           }
         }
       }
     }
-    ACC_STAMP_FIRST(11);
     // ---- right-hand side rows lane, lane+64:  y = v - Q u e   (v_i -= w r Ji, v_j += w r Jj; :314-316, :512)
 #pragma unroll
     for (int g = 0; g < 2; g++) {
@@ -1210,39 +1134,18 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
           for (int q = NSL; q < nslot; q++) acc += scr[26 * SLD + q] * scr[(12 + a) * SLD + q] + scr[27 * SLD + q] * scr[(18 + a) * SLD + q];
           v -= acc;
         }
-        if constexpr (LDSFOLD) {
-          float* yp = tri + nt + r;
-          if (fresh) *yp = v;                                    // (wave-uniform)
-          else *yp += v;
-        } else yreg[g] += v;
+        float* yp = tri + nt + r;
+        if (fresh) *yp = v;                                      // (wave-uniform)
+        else *yp += v;
       }
     }
     fresh = false;
     wave_lds_sync();
-    ACC_STAMP_PATCH(4);
   }
 
-  // ---- register form: every wave parks its register copy in its own LDS slab (all waves at once); LDS form: the slab is
-  //      complete (a wave without a regular patch clears it).  Then the workgroup adds the slabs and the atomic-path system
-  //      in a fixed order and writes the compact partial
-  if (N > 0) {
-    if constexpr (LDSFOLD) {
-      if (fresh) for (int i = lane; i < nt + n6; i += 64) tri[i] = 0.0f;
-    } else {
-      if (lane < 36) {
-        int blk = 0;
-#pragma unroll
-        for (int fr = 0; fr < NMAX; fr++) {
-#pragma unroll
-          for (int fc = 0; fc <= fr; fc++, blk++) {
-            if (fr < N) tri[blk * 36 + lane] = Sreg[blk];
-          }
-        }
-      }
-#pragma unroll
-      for (int g = 0; g < 2; g++) if (lane + 64 * g < n6) tri[nt + lane + 64 * g] = yreg[g];
-    }
-  }
+  // ---- the slab is complete (a wave without a regular patch clears it).  Then the workgroup adds the slabs and the atomic-path
+  //      system in a fixed order and writes the compact partial
+  if (N > 0 && fresh) for (int i = lane; i < nt + n6; i += 64) tri[i] = 0.0f;
   __syncthreads();
   if (N > 0) {
     float* out = partials + (int64_t)blockIdx.x * (nt + n6);
@@ -1274,7 +1177,6 @@ __global__ __launch_bounds__(WAVES * 64) void k_ba_accumulate_reg(
       out[i] = v;
     }
   }
-  ACC_STAMP(7);
 }
 
 // S = sum of the compact partials, mirrored; S_dd <- S_dd*(1+1e-4)+1 (ba_cuda.cu:517-518); y = sum.
@@ -1409,16 +1311,10 @@ __global__ void k_ba_damp(float* __restrict__ S, int N, float ep, const float* _
 
 // ------------------------------------------------------------------------------------------------- solve
 // One workgroup.  A (n6+1) x LD lower-triangular working matrix lives in LDS; row n6 holds y^T, so after the
-// factorisation row n6 is z = L^{-1} y.  Blocked by the 6x6 pose blocks.  There is no serial section: every
-// thread that owns a panel row factors the 6x6 diagonal block itself, in registers, from the same LDS values
-// (broadcast reads) — cheaper than one lane doing it followed by a barrier.
-#ifndef DEVO_SOLVE_THREADS
-#define DEVO_SOLVE_THREADS 1024
-#endif
-constexpr int SOLVE_THREADS = DEVO_SOLVE_THREADS;
-#ifndef DEVO_SOLVE_LOOKAHEAD
-#define DEVO_SOLVE_LOOKAHEAD 1                      // 0: every panel thread factors the diagonal block itself (round 1; A/B builds)
-#endif
+// factorisation row n6 is z = L^{-1} y.  Blocked by the 6x6 pose blocks; the diagonal block of the next step is factored by a
+// look-ahead wave while the others run the trailing update (round 1's form, in which every panel thread factored it itself, is in git
+// history).
+constexpr int SOLVE_THREADS = 1024;
 
 __device__ __forceinline__ bool chol6(float L[6][6], float inv[6]) {   // in-register lower Cholesky of a 6x6 block
   bool ok = true;                                                      // inv[c] = 1 / L[c][c]
@@ -1450,16 +1346,12 @@ __host__ __device__ inline int solve_ld(int n6) {
   return n6 + 2;
 }
 
-__device__ unsigned long long g_solve_stamps[16];
-__device__ unsigned long long g_solve_arrive[24 * 16];      // debug (DEVO_BA_TRACE=7): when every wave reached the barrier of every block step
-// debug (DEVO_BA_TRACE): cycle stamps of the last solve
-
 // GLOBAL (more than BA_MAXN_LDS optimised poses: the image does not fit the LDS): the same algorithm IN PLACE on the global image
 // (row stride n6 + 1; one workgroup = one CU = one L1, workgroup barriers order its global accesses); only the factored diagonal
 // blocks, their inverses and the solution stay in LDS.  Slower by the latency ratio, correct for any N the LDS tables hold.
 template <bool GLOBAL>
 __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, const float* __restrict__ y, int N,
-                                                              float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag, int stamps) {
+                                                              float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag) {
   extern __shared__ __attribute__((aligned(16))) float solve_smem[];
   __shared__ int s_fail;
   // LDS image: rows x LD with an EVEN row stride (the global image k_ba_reduce wrote has n6 + 1): panel columns start at even
@@ -1470,7 +1362,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
   float* Li = Ld + N * 36;                      // [N][36] their inverses (for the back-substitution)
   float* xs = Li + N * 36;                      // [n6] solution
   const int tid = threadIdx.x;
-  const unsigned long long st0 = stamps ? __builtin_readcyclecounter() : 0ull;      // (s_memtime stalls: debug only)
   if (tid == 0) s_fail = 0;
   if (!GLOBAL) {
     // k_ba_reduce wrote this very image (rows x LD, the right-hand side is row n6); eight loads in flight per thread
@@ -1488,16 +1379,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
       }
     }
   }
-  // This thread's 2x2 tile (ty >= tx) of the trailing lower triangle, relative to the trailing corner — the same for
-  // every block step; 2x2 register tiles halve the LDS reads of the update (12 + 12 operands for 4 entries).
-  auto tile_of = [](int t, int& yy, int& xx) {
-    yy = (int)((sqrtf(8.0f * (float)t + 1.0f) - 1.0f) * 0.5f);
-    while (yy * (yy + 1) / 2 > t) yy--;
-    while ((yy + 1) * (yy + 2) / 2 <= t) yy++;
-    xx = t - yy * (yy + 1) / 2;
-  };
-  int ty, tx;                                  // this thread's first tile: the only one it has for N <= 14 at 1024 threads
-  tile_of(tid, ty, tx);
   __syncthreads();
   if (iter == 0 && tid == 0 && status_flag) *status_flag = meta->fail < 0 ? -1 : 0;      // (the call's status word starts here: no fill in front of the call)
   if (meta->fail) {                              // an earlier iteration broke down: the reference call has thrown by now
@@ -1505,9 +1386,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
     return;
   }
 
-  const unsigned long long st1 = stamps ? __builtin_readcyclecounter() : 0ull;
-  unsigned long long ph_panel = 0, ph_update = 0, ph_q1 = 0, ph_q2 = 0;
-#if DEVO_SOLVE_LOOKAHEAD
   // Look-ahead: the 6x6 diagonal block of step jb + 1 is brought up to date and factored by ONE wave (the last) while the other
   // waves run the trailing update of step jb — the serial rsq chain of the block factorisation leaves the panel phase.  The
   // tiles of that block (t < 6) are nobody else's; its updated values only ever feed the factorisation, so they are not written
@@ -1543,7 +1421,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
   }
   __syncthreads();
   for (int jb = 0; jb < N; jb++) {
-    const unsigned long long pa = stamps ? __builtin_readcyclecounter() : 0ull;
     const int j0 = 6 * jb;
     const int r = j0 + 6 + tid;                  // this thread's panel row (if any)
     if (r < rows) {                              // panel:  x L_bb^T = A[r][block], L_bb from the look-ahead (broadcast reads)
@@ -1565,9 +1442,8 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
       for (int c = 0; c < 6; c++) A[r * LD + j0 + c] = x[c];
     }
     __syncthreads();
-    const unsigned long long pb = stamps ? __builtin_readcyclecounter() : 0ull;
     const bool next = jb + 1 < N;
-    if (next && (tid >> 6) == LA_WAVE && stamps != 3 && stamps != 4) {                // (stamps == 3: timing experiment without the look-ahead factorisation)
+    if (next && (tid >> 6) == LA_WAVE) {
       const int l = tid & 63, a = l / 6, c = l % 6, j1 = j0 + 6;
       if (l < 36 && c <= a) {
         float acc = 0.0f;
@@ -1584,12 +1460,11 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
     // order.  Per lane 4 operand values and 4 result values come out of LDS (the 2 x 2 register tiles of round 2 read 28 values for 4
     // results), all conflict-free with the row stride of solve_ld().  Inputs = the panel columns, outputs = the columns to their
     // right: disjoint.  The 6 x 6 block the look-ahead wave factors meanwhile is not written back (nobody reads it again).
-    if ((tid >> 6) != LA_WAVE && stamps != 2 && stamps != 4) {
+    if ((tid >> 6) != LA_WAVE) {
       const int base = j0 + 6, T = (rows - base + 15) >> 4, ntl = T * (T + 1) / 2;
       for (int t = tl_wv; t < ntl; t += LA_WAVE) {
         int I = tl_I, J = tl_J;                                    // the wave's first tile: the same (I, J) in every step
         if (t != tl_wv) { I = 0; while ((I + 1) * (I + 2) / 2 <= t) I++; J = t - I * (I + 1) / 2; }      // (more than 14 poses only)
-        const unsigned long long q0 = (stamps && tid == 0) ? __builtin_readcyclecounter() : 0ull;
         const int rb = base + 16 * I, cb = base + 16 * J;
         const float* pr = A + __mul24(min(rb + tl_mm, rows - 1), LD) + j0;      // operand rows (clamped: their products only reach masked results)
         const float* pc_ = A + __mul24(min(cb + tl_mm, rows - 1), LD) + j0;
@@ -1608,89 +1483,14 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
           dst[i] = ok ? p0 + i * LD : s_dump + (tid & 63);
           c[i] = *dst[i];
         }
-        const unsigned long long q1 = (stamps && tid == 0) ? __builtin_readcyclecounter() : 0ull;
         c = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c, 0, 0, 0);
         c = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, c, 0, 0, 0);
 #pragma unroll
         for (int i = 0; i < 4; i++) *dst[i] = c[i];
-        if (stamps && tid == 0) { const unsigned long long q2 = __builtin_readcyclecounter(); ph_q1 += q1 - q0; ph_q2 += q2 - q1; }
       }
     }
     __syncthreads();
-    if (stamps) { const unsigned long long pc = __builtin_readcyclecounter(); ph_panel += pb - pa; ph_update += pc - pb; }
   }
-#else
-  for (int jb = 0; jb < N; jb++) {
-    const unsigned long long pa = stamps ? __builtin_readcyclecounter() : 0ull;
-    const int j0 = 6 * jb;
-    const int r = j0 + 6 + tid;                  // this thread's panel row (if any)
-    if (r < rows || tid == 0) {
-      float L[6][6];
-#pragma unroll
-      for (int a = 0; a < 6; a++)
-#pragma unroll
-        for (int c = 0; c <= a; c++) L[a][c] = A[(j0 + a) * LD + j0 + c];
-      float inv[6];
-      const bool ok = chol6(L, inv);
-      if (tid == 0) {
-        if (!ok) s_fail = 1;
-#pragma unroll
-        for (int a = 0; a < 6; a++)
-#pragma unroll
-          for (int c = 0; c <= a; c++) Ld[jb * 36 + a * 6 + c] = (a == c) ? inv[a] : L[a][c];
-      }
-      if (r < rows) {                            // panel:  x L_bb^T = A[r][block]
-        float x[6];
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-          float v = A[r * LD + j0 + c];
-#pragma unroll
-          for (int k = 0; k < c; k++) v -= x[k] * L[c][k];
-          x[c] = v * inv[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 6; c++) A[r * LD + j0 + c] = x[c];
-      }
-    }
-    __syncthreads();
-    const unsigned long long pb = stamps ? __builtin_readcyclecounter() : 0ull;
-    // trailing update of the lower triangle (and of the rhs row) in 2x2 tiles; inputs = the panel columns, outputs =
-    // the columns to their right (disjoint), so everything is fetched before anything is written back
-    const int rem = rows - (j0 + 6);
-    const int nt = (rem + 1) / 2;                // tiles per side
-    const int ntiles = nt * (nt + 1) / 2;
-    for (int k = 0; tid + SOLVE_THREADS * k < ntiles; k++) {
-      const int t = tid + SOLVE_THREADS * k;
-      int yy, xx;
-      if (k == 0) { yy = ty; xx = tx; }
-      else tile_of(t, yy, xx);                   // large N only: more tiles than threads
-      const int r0 = j0 + 6 + 2 * yy, c0 = j0 + 6 + 2 * xx;
-      const bool r1ok = r0 + 1 < rows, c1ok = c0 + 1 < n6;          // second row / column inside the matrix
-      const int r1 = r1ok ? r0 + 1 : r0, c1 = c1ok ? c0 + 1 : c0;
-      if (c0 >= n6) continue;                    // the rhs row has no diagonal entry
-      float pa0[6], pa1[6], pb0[6], pb1[6];
-#pragma unroll
-      for (int q = 0; q < 6; q++) {
-        pa0[q] = A[r0 * LD + j0 + q]; pa1[q] = A[r1 * LD + j0 + q];
-        pb0[q] = A[c0 * LD + j0 + q]; pb1[q] = A[c1 * LD + j0 + q];
-      }
-      float o00 = A[r0 * LD + c0], o01 = A[r0 * LD + c1], o10 = A[r1 * LD + c0], o11 = A[r1 * LD + c1];
-      float v00 = 0.0f, v01 = 0.0f, v10 = 0.0f, v11 = 0.0f;
-#pragma unroll
-      for (int q = 0; q < 6; q++) {
-        v00 += pa0[q] * pb0[q]; v01 += pa0[q] * pb1[q];
-        v10 += pa1[q] * pb0[q]; v11 += pa1[q] * pb1[q];
-      }
-      A[r0 * LD + c0] = o00 - v00;                                   // c0 <= r0 always (xx <= yy)
-      if (c1ok && c1 <= r0) A[r0 * LD + c1] = o01 - v01;             // above the diagonal on diagonal tiles: skip
-      if (r1ok) A[r1 * LD + c0] = o10 - v10;
-      if (r1ok && c1ok) A[r1 * LD + c1] = o11 - v11;
-    }
-    __syncthreads();
-    if (stamps) { const unsigned long long pc = __builtin_readcyclecounter(); ph_panel += pb - pa; ph_update += pc - pb; }
-  }
-#endif
-  const unsigned long long st2 = stamps ? __builtin_readcyclecounter() : 0ull;
   if (s_fail) {
     // breakdown: dX = 0 (devo/ba.py:16-20: CholeskySolver returns zeros, no gradient through the solve) — the callers of the
     // differentiable path copy / read dX afterwards, and the workspace is not zero-initialised
@@ -1726,7 +1526,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
   // waves are done).  x_b = L_bb^-T z_b from the inverse block, then the lanes update their rows of z.  The solution is
   // collected in LDS (a global store inside the loop would put a vmcnt wait into every step's fence).
   if (tid >= 64) return;
-  const unsigned long long st3 = stamps ? __builtin_readcyclecounter() : 0ull;
   // Register form: lane r keeps z[r] and z[r + 64] (n6 <= 128 here).  One wave issues one instruction every ~5 cycles, so
   // a step is priced by its instruction count: the block's six z values come through v_readlane, lane c < 6 forms x_b[c]
   // from column c of the inverse block (6 FMAs), x_b goes back to all lanes through v_readlane, every lane updates its own
@@ -1807,7 +1606,6 @@ __global__ __launch_bounds__(SOLVE_THREADS) void k_ba_solve_t(const float* S, co
     }
   }
   for (int i = tid; i < n6; i += 64) dX[i] = xs[i];
-  if (stamps && tid == 0) { g_solve_stamps[0] = st0; g_solve_stamps[1] = st1; g_solve_stamps[2] = st2; g_solve_stamps[3] = st3; g_solve_stamps[4] = __builtin_readcyclecounter(); g_solve_stamps[5] = ph_panel; g_solve_stamps[6] = ph_update; g_solve_stamps[8] = ph_q1; g_solve_stamps[9] = ph_q2; }
 }
 
 
@@ -1838,7 +1636,7 @@ typedef float solve_f2 __attribute__((ext_vector_type(2)));
 struct BaRetract { float* poses; float* patches; const float* patch_rec; const float* patch_col; const int* kx; int P, t0; };
 template <bool FUSED>
 __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S, const float* __restrict__ y, int N,
-                                                    float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag, int stamps,
+                                                    float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag,
                                                     const BaRetract& ra, int G = 0) {   // G > 0: the launch's first G workgroups solve (others ride along)
   extern __shared__ __attribute__((aligned(16))) float A[];
   const bool lead = blockIdx.x == 0;                              // (the only workgroup of the unfused launch)
@@ -1854,11 +1652,10 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
   float* Li = Ld + N * 36;                      // [N][36] their inverses (for the back-substitution)
   float* xs = Li + N * 36;                      // [n6] solution
   const int tid = threadIdx.x, wv = tid >> 6, ln = tid & 63;
-  constexpr int CHAIN = 15, INVW = 14, NTW = 12;                 // the chain wave, (stamps: the last tile wave), the number of tile waves
+  constexpr int CHAIN = 15, NTW = 12;                            // the chain wave, the number of tile waves
   const bool tile_wave = (wv & 3) != 3;
   const int tw = wv - (wv >> 2);                                 // tile waves numbered 0 .. 11
   if (wv == CHAIN) __builtin_amdgcn_s_setprio(3);
-  const unsigned long long st0 = stamps ? __builtin_readcyclecounter() : 0ull;
   if (tid == 0) s_fail = 0;
   const int failed_before = meta->fail;           // (in flight with the matrix: a load after the barrier would add its whole latency)
   {
@@ -1885,8 +1682,6 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
     if (lead && tid == 0 && failed_before < 0 && status_flag) *status_flag = -1;  // (or the workspace was never prepared)
     return;
   }
-  const unsigned long long st1 = stamps ? __builtin_readcyclecounter() : 0ull;
-  unsigned long long ph_work = 0;
   auto lane_value = [](float v, int lane) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane)); };
   auto load_factor = [&](int jb, float Lb[6][6], float inv[6]) {        // broadcast reads
 #pragma unroll
@@ -2004,8 +1799,7 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
   }
   __syncthreads();
   // every role runs its own loop (a taken branch costs ~30 cycles: no role dispatch inside the steps); N barriers each
-  auto step_barrier = [&](int jb = -1) {
-    if (stamps == 7 && ln == 0 && jb >= 0 && jb < 24) g_solve_arrive[jb * 16 + wv] = __builtin_readcyclecounter();
+  auto step_barrier = [&] {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -2013,8 +1807,7 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
   if (wv == CHAIN) {
     const int la = ln < 36 ? ln / 6 : 5, lc = ln < 36 ? ln % 6 : 5;
     for (int jb = 0; jb < N; jb++) {
-      const unsigned long long pa = stamps == 1 ? __builtin_readcyclecounter() : 0ull;
-      if (jb + 1 < N && stamps != 3) {                              // (DEVO_BA_TRACE=3 / 2: timing experiments without the chain / the tiles)
+      if (jb + 1 < N) {
         const int j0 = 6 * jb, j1 = j0 + 6;
         const float* pr = A + (j1 + la) * LD + j0;
         const float* pc = A + (j1 + lc) * LD + j0;
@@ -2034,17 +1827,15 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
           for (int c = 0; c <= a; c++) L[a][c] = lane_value(d, a * 6 + c);
         factor_and_store(L, jb + 1);
       }
-      if (stamps == 1) ph_work += __builtin_readcyclecounter() - pa;
-      step_barrier(jb);
+      step_barrier();
     }
   } else if (tile_wave) {
     for (int jb = 0; jb < N; jb++) {
-      const unsigned long long pa = stamps == 1 ? __builtin_readcyclecounter() : 0ull;
       const int T = (rows - 6 * jb - 6 + 15) >> 4, ntl = T * (T + 1) / 2;
       // the inverse of L_bb (for the back-substitution) is the job of the first tile wave WITHOUT a tile in this step (the last one while
       // all have tiles): in the late steps, where one to three tiles are left, it is not on the step's critical path
       const bool do_inv = tw == min(ntl, NTW - 1);
-      if ((tw < ntl || do_inv) && stamps != 2) {
+      if (tw < ntl || do_inv) {
         float Lb[6][6], inv[6];
         load_factor(jb, Lb, inv);
         if (tw < ntl) do_tile(my_tile, jb, Lb, inv);
@@ -2065,14 +1856,11 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
           }
         }
       }
-      if (stamps == 1) ph_work += __builtin_readcyclecounter() - pa;
-      step_barrier(jb);
+      step_barrier();
     }
   } else {
-    for (int jb = 0; jb < N; jb++) step_barrier(jb);
+    for (int jb = 0; jb < N; jb++) step_barrier();
   }
-  const unsigned long long st2 = stamps ? __builtin_readcyclecounter() : 0ull;
-  if (stamps && ln == 0 && (wv == CHAIN || wv == 0 || wv == INVW)) g_solve_stamps[wv == CHAIN ? 6 : wv == 0 ? 8 : 9] = ph_work;
   if (s_fail) {                                                    // (FUSED: every workgroup sees the same breakdown; nobody retracts)
     if (lead) {
       for (int i = tid; i < 6 * N; i += 1024) dX[i] = 0.0f;       // (see k_ba_solve)
@@ -2143,7 +1931,6 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
   }
   wave_lds_sync();
   if (lead) for (int i = tid; i < n6; i += 64) dX[i] = xs[i];
-  if (stamps && lead && tid == 0) { g_solve_stamps[0] = st0; g_solve_stamps[1] = st1; g_solve_stamps[2] = st2; g_solve_stamps[3] = st2; g_solve_stamps[4] = __builtin_readcyclecounter(); g_solve_stamps[5] = 0; }
   }
   if constexpr (FUSED) {
     // ---- retraction with the solution in LDS (k_ba_retract's arithmetic in its order: the same bits).  One wave per patch, the loads of
@@ -2193,13 +1980,13 @@ __device__ __forceinline__ void ba_solve_chain_body(const float* __restrict__ S,
   }
 }
 __global__ __launch_bounds__(1024) void k_ba_solve_chain(const float* __restrict__ S, const float* __restrict__ y, int N,
-                                                         float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag, int stamps) {
-  ba_solve_chain_body<false>(S, y, N, dX, meta, iter, status_flag, stamps, BaRetract{});
+                                                         float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag) {
+  ba_solve_chain_body<false>(S, y, N, dX, meta, iter, status_flag, BaRetract{});
 }
 __global__ __launch_bounds__(1024) void k_ba_solve_retract(const float* __restrict__ S, const float* __restrict__ y, int N,
-                                                           float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag, int stamps,
+                                                           float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag,
                                                            BaRetract ra) {
-  ba_solve_chain_body<true>(S, y, N, dX, meta, iter, status_flag, stamps, ra);
+  ba_solve_chain_body<true>(S, y, N, dX, meta, iter, status_flag, ra);
 }
 
 // k_ba_solve_retract with the ordering step of the NEXT lookup's locality plan (corr_plan.h) in the workgroups behind the G solving ones: the
@@ -2207,15 +1994,15 @@ __global__ __launch_bounds__(1024) void k_ba_solve_retract(const float* __restri
 // lookup of update iteration k + 1 can take the plan made from iteration k's coordinates (devo_ba_forward_prepared_delta_plan).
 template <int CACHE>
 __global__ __launch_bounds__(1024) void k_ba_solve_retract_order(const float* __restrict__ S, const float* __restrict__ y, int N,
-                                                                 float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag, int stamps,
+                                                                 float* __restrict__ dX, BaMeta* meta, int iter, int* status_flag,
                                                                  BaRetract ra, int G, const int* __restrict__ bins, int BE, int nbins,
                                                                  int* __restrict__ order, int starts) {
   if ((int)blockIdx.x >= G) { corr_order_body<CACHE>(bins, BE, nbins, order, (int)blockIdx.x - G, (int)gridDim.x - G, starts != 0); return; }
-  ba_solve_chain_body<true>(S, y, N, dX, meta, iter, status_flag, stamps, ra, G);
+  ba_solve_chain_body<true>(S, y, N, dX, meta, iter, status_flag, ra, G);
 }
 
 static_assert(SOLVE_THREADS == 1024, "k_ba_solve_chain is written for 16 waves");
-typedef void (*solve_fn_t)(const float*, const float*, int, float*, BaMeta*, int, int*, int);
+typedef void (*solve_fn_t)(const float*, const float*, int, float*, BaMeta*, int, int*);
 static solve_fn_t ba_solve_fn(int N) {
   static const bool v1 = getenv("DEVO_BA_SOLVE_V1") != nullptr;   // A/B and test switch: the two-barrier form for every N
   return (6 * N <= 128 && !v1) ? k_ba_solve_chain : k_ba_solve;
@@ -2693,24 +2480,17 @@ struct BaLayout {
   size_t meta, rank, counts, cursor, ku, perm_a, perm_b, kx, range, partials, S, y, dX, patch_rec, edge_ej, prec, ybar, total, partials_bytes;
   int max_seg, n_part;
 };
-// Form of the register-path accumulate kernel (N <= 16) and its waves per workgroup — DEVO_BA_REGFOLD=1: the register fold.
-struct AccCfg { int waves; bool ldsfold; };
-static AccCfg acc_cfg(int N) {
-  static const bool regfold = getenv("DEVO_BA_REGFOLD") != nullptr;
-  if (regfold || N > 16) return {REG_WAVES, false};
-  return {N <= 11 ? 8 : N <= 14 ? 6 : 4, true};               // what 160 KB of LDS hold: WAVES slabs + scratch + the atomic-path system
-}
-static size_t acc_reg_lds_bytes(int N, const AccCfg& c) {
-  const size_t n6 = 6 * (size_t)N;
-  return sizeof(float) * (n6 * (n6 + 1) + n6 + c.waves * n6 + 4 + (size_t)c.waves * SCR_ROWS * scr_ld(c.ldsfold) +
-                          c.waves * ((size_t)N * (N + 1) / 2 * 36 + n6));
+// Waves per workgroup of the register-path accumulate kernel (N <= 16): what 160 KB of LDS hold — WAVES slabs + scratch + the atomic-path
+// system.  (Above 16 poses: the 4 that size the general kernel's partials.)
+static int acc_waves(int N) { return N <= 11 ? 8 : N <= 14 ? 6 : 4; }
+static size_t acc_reg_lds_bytes(int N) {
+  const size_t n6 = 6 * (size_t)N, waves = acc_waves(N);
+  return sizeof(float) * (n6 * (n6 + 1) + n6 + waves * n6 + 4 + waves * SCR_ROWS * SCR_LD + waves * ((size_t)N * (N + 1) / 2 * 36 + n6));
 }
 typedef void (*acc_fn_t)(const float*, const float*, const float*, TargetSrc, const float*, const float*, const int64_t*,
                          const int64_t*, const int64_t*, const int*, const int*, BaMeta*, int, int, int, float*, float*,
                          float*, int, int, int);
-static acc_fn_t acc_reg_fn(int N, const AccCfg& c) {
-  if (!c.ldsfold) return (N <= 8) ? k_ba_accumulate_reg<8, 4, false> : (N <= 11) ? k_ba_accumulate_reg<11, 4, false> :
-                         (N <= 14) ? k_ba_accumulate_reg<14, 4, false> : k_ba_accumulate_reg<16, 4, false>;
+static acc_fn_t acc_reg_fn(int N) {
   return (N <= 8) ? k_ba_accumulate_reg<8, 8, true> : (N <= 11) ? k_ba_accumulate_reg<11, 8, true> :
          (N <= 14) ? k_ba_accumulate_reg<14, 6, true> : k_ba_accumulate_reg<16, 4, true>;
 }
@@ -2721,8 +2501,8 @@ static BaLayout ba_layout(int E, int Np, int N) {
   auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
   L.max_seg = E < Np ? E : Np;
   if (L.max_seg < 1) L.max_seg = 1;
-  const int acc_waves = acc_cfg(N).waves;
-  int want = (L.max_seg + acc_waves - 1) / acc_waves;
+  const int waves = acc_waves(N);
+  int want = (L.max_seg + waves - 1) / waves;
   L.n_part = want < ACC_MAX_WG ? (want < 1 ? 1 : want) : ACC_MAX_WG;
   const size_t n6 = 6 * (size_t)N;
   L.meta = take(sizeof(BaMeta));
@@ -2759,13 +2539,6 @@ static unsigned next_pow2(unsigned v) { unsigned p = 1; while (p < v) p <<= 1; r
 using namespace devo;
 
 extern "C" {
-#ifdef DEVO_PREP_TRACE
-int devo_debug_prep_trace(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_prep_trace), sizeof(g_prep_trace)); }
-#endif
-#ifdef DEVO_ACC_TRACE
-int devo_debug_acc_trace(unsigned long long* out) { return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_acc_trace), sizeof(g_acc_trace)); }
-#endif
-
 size_t devo_ba_workspace_bytes(int E, int Np, int N) {
   if (E < 0 || Np < 0 || N < 0 || N > BA_MAXN) return 0;
   return ba_layout(E, Np, N).total;
@@ -3019,9 +2792,8 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
   const size_t solve_lds = big ? sizeof(float) * (72 * (size_t)N + n6 + 4) : sizeof(float) * ((n6 + 1) * (size_t)solve_ld((int)n6) + 72 * (size_t)N + n6 + 4);
   static const bool force_generic = getenv("DEVO_BA_GENERIC") != nullptr;   // test switch: the general accumulate kernel for every N
   const bool use_reg = (N <= 16) && !force_generic;
-  const AccCfg cfg = acc_cfg(N);
-  const size_t acc_lds_used = use_reg ? acc_reg_lds_bytes(N, cfg) : acc_lds;
-  acc_fn_t acc_fn = use_reg ? acc_reg_fn(N, cfg) : big ? k_ba_accumulate_t<true> : k_ba_accumulate;
+  const size_t acc_lds_used = use_reg ? acc_reg_lds_bytes(N) : acc_lds;
+  acc_fn_t acc_fn = use_reg ? acc_reg_fn(N) : big ? k_ba_accumulate_t<true> : k_ba_accumulate;
   // what this call runs (devo_ba_last_path: accumulate kind | 4 * solve kind) and, once per process, a line when the system leaves the LDS
   g_ba_path = (use_reg ? 0 : big ? 2 : 1) | ((big ? 2 : (6 * N <= 128 ? 0 : 1)) << 2);
   if (big) {
@@ -3037,9 +2809,8 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
   // own patches).  G: one patch per wave, at most 128 workgroups.  DEVO_BA_FUSE_RETRACT=0: the two launches of rounds 1-5.
   static const bool fuse_env = [] { const char* e = getenv("DEVO_BA_FUSE_RETRACT"); return !(e && e[0] == '0'); }();
   const bool fuse_retract = fuse_env && N > 0 && solve_fn == k_ba_solve_chain;
-  static const int wgs_env = [] { const char* e = getenv("DEVO_BA_RETRACT_WGS"); return e ? atoi(e) : 0; }();   // (tuning switch)
   // (measured at cfg2, 1 440 patches, rocprofv3: G = 1 / 4 / 12 / 23 / 45 / 90 / 180 -> 93.9 / 37.5 / 24.7 / 21.3 / 19.6 / 19.2 / 19.1 us; the solver alone 19.5)
-  const int retract_wgs = wgs_env > 0 ? wgs_env : L.max_seg <= 16 ? 1 : (L.max_seg + 15) / 16 > 128 ? 128 : (L.max_seg + 15) / 16;
+  const int retract_wgs = L.max_seg <= 16 ? 1 : (L.max_seg + 15) / 16 > 128 ? 128 : (L.max_seg + 15) / 16;
   if (fuse_retract && solve_lds > 64 * 1024 &&
       hipFuncSetAttribute((const void*)k_ba_solve_retract, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds) != hipSuccess) {
     (void)hipGetLastError();
@@ -3054,23 +2825,20 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
       return DEVO_ERR_LAUNCH;
     }
   }
-  // the general kernel (N > 16) leaves the Schur term to ONE product afterwards (k_ba_schur); DEVO_BA_SCHUR_INLINE=1: per patch, in LDS
-  static const bool schur_inline = getenv("DEVO_BA_SCHUR_INLINE") != nullptr;
-  const bool defer = !use_reg && N > 0 && (!schur_inline || big);
+  // the general kernel (N > 16) leaves the Schur term to ONE product afterwards (k_ba_schur)
+  const bool defer = !use_reg && N > 0;
   for (int it = 0; it < iterations; it++) {
     if (big && hipMemsetAsync(S, 0, sizeof(float) * (n6 + 1) * (n6 + 1), st) != hipSuccess) { set_error("devo_ba_forward: memset failed"); return DEVO_ERR_LAUNCH; }
-    hipLaunchKernelGGL(acc_fn, dim3(L.n_part), dim3(use_reg ? cfg.waves * 64 : ACC_THREADS), acc_lds_used, st, poses, patches, intrinsics, target,
+    hipLaunchKernelGGL(acc_fn, dim3(L.n_part), dim3(use_reg ? acc_waves(N) * 64 : ACC_THREADS), acc_lds_used, st, poses, patches, intrinsics, target,
                        weight, lmbda, ii, jj, kk, perm_b, counts, meta, P, t0, N, big ? S : partials, patch_rec, edge_ej, it | (defer ? 1 << 16 : 0), ba_sig(E, N), L.max_seg);
     if ((rc = check_launch("devo_ba_forward(accumulate)"))) return rc;
     if (N > 0) {
       if (!big) hipLaunchKernelGGL(k_ba_reduce, dim3((unsigned)((N * (N + 1) / 2 * 36 + n6 + 63) / 64)), dim3(512), 0, st, partials, L.n_part, N, S, y, defer ? BA_EP_DEFERRED : ep);
       if (defer) ba_deferred_schur(st, patch_rec, edge_ej, meta, N, L.max_seg, S, ep, partials, L.partials_bytes);
       if ((rc = check_launch("devo_ba_forward(reduce)"))) return rc;
-      static const bool ba_trace = getenv("DEVO_BA_TRACE") != nullptr;
-      static const int ba_trace_mode = ba_trace ? (atoi(getenv("DEVO_BA_TRACE")) > 1 ? atoi(getenv("DEVO_BA_TRACE")) : 1) : 0;
       const long long order_ept = ((long long)E + ORDER_THREADS - 1) / ORDER_THREADS;
       if (fuse_retract && rider.plan && order_ept <= 32) {        // the next lookup's plan rides on this launch (once per call)
-        typedef void (*ride_fn_t)(const float*, const float*, int, float*, BaMeta*, int, int*, int, BaRetract, int, const int*, int, int, int*, int);
+        typedef void (*ride_fn_t)(const float*, const float*, int, float*, BaMeta*, int, int*, BaRetract, int, const int*, int, int, int*, int);
         ride_fn_t ride = order_ept <= 8 ? k_ba_solve_retract_order<8> : order_ept <= 16 ? k_ba_solve_retract_order<16> :
                          order_ept <= 24 ? k_ba_solve_retract_order<24> : k_ba_solve_retract_order<32>;
         if (solve_lds > 48 * 1024 && hipFuncSetAttribute((const void*)ride, hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds) != hipSuccess) {
@@ -3079,37 +2847,14 @@ static int ba_forward_impl(float* poses, float* patches, const float* intrinsics
           return DEVO_ERR_LAUNCH;
         }
         hipLaunchKernelGGL(ride, dim3((unsigned)(retract_wgs + corr_order_workgroups(E, rider.nbins))), dim3(SOLVE_THREADS), solve_lds, st, S, y, N, dX, meta, it,
-                           status_flag, ba_trace_mode, BaRetract{poses, patches, patch_rec, edge_ej, kx, P, t0}, retract_wgs, (const int*)(rider.plan + E + 1), E,
+                           status_flag, BaRetract{poses, patches, patch_rec, edge_ej, kx, P, t0}, retract_wgs, (const int*)(rider.plan + E + 1), E,
                            rider.nbins, rider.plan, rider.starts);
         rider.plan = nullptr;                                     // done
       } else if (fuse_retract)
-        hipLaunchKernelGGL(k_ba_solve_retract, dim3((unsigned)retract_wgs), dim3(SOLVE_THREADS), solve_lds, st, S, y, N, dX, meta, it, status_flag, ba_trace_mode,
+        hipLaunchKernelGGL(k_ba_solve_retract, dim3((unsigned)retract_wgs), dim3(SOLVE_THREADS), solve_lds, st, S, y, N, dX, meta, it, status_flag,
                            BaRetract{poses, patches, patch_rec, edge_ej, kx, P, t0});
       else
-        hipLaunchKernelGGL(solve_fn, dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, y, N, dX, meta, it, status_flag, ba_trace_mode);
-      if (ba_trace) {
-        unsigned long long h[16];
-        (void)hipStreamSynchronize(st);
-        (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_solve_stamps), sizeof(h));
-        if (solve_fn == k_ba_solve_chain && ba_trace_mode == 7) {
-          unsigned long long arr[24 * 16];
-          (void)hipMemcpyFromSymbol(arr, HIP_SYMBOL(g_solve_arrive), sizeof(arr));
-          fprintf(stderr, "[ba trace] arrival at the step barrier, cycles after the step's first arrival (waves 0..15; * = last), and the step's length:\n");
-          unsigned long long prev_last = 0;
-          for (int jb = 0; jb < N && jb < 24; jb++) {
-            unsigned long long lo = ~0ull, hi = 0; int last = 0;
-            for (int w = 0; w < 16; w++) { const unsigned long long v = arr[jb * 16 + w]; if (v < lo) lo = v; if (v > hi) { hi = v; last = w; } }
-            fprintf(stderr, "  step %2d:", jb);
-            for (int w = 0; w < 16; w++) fprintf(stderr, " %5llu%s", arr[jb * 16 + w] - lo, w == last ? "*" : " ");
-            fprintf(stderr, "   | %llu\n", prev_last ? hi - prev_last : 0ull);
-            prev_last = hi;
-          }
-        }
-        if (solve_fn == k_ba_solve_chain)
-          fprintf(stderr, "[ba trace] solve (one barrier per step): load %llu, factorisation %llu, back substitution %llu cycles (work inside the steps: chain wave %llu, tile wave 0 %llu, inverse wave %llu)\n", h[1] - h[0], h[2] - h[1], h[4] - h[3], h[6], h[8], h[9]);
-        else
-          fprintf(stderr, "[ba trace] solve: load %llu, factorisation %llu, block inverses %llu, back substitution %llu cycles (factorisation: panel %llu + update %llu; wave 0's tile: operands + results in %llu, products + stores %llu)\n", h[1] - h[0], h[2] - h[1], h[3] - h[2], h[4] - h[3], h[5], h[6], h[8], h[9]);
-      }
+        hipLaunchKernelGGL(solve_fn, dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, y, N, dX, meta, it, status_flag);
       if ((rc = check_launch("devo_ba_forward(solve)"))) return rc;
     }
     if (!fuse_retract) {
@@ -3182,9 +2927,8 @@ int devo_ba_solve_terms(const float* terms, const float* lmbda, const int64_t* i
   const size_t acc_lds = sizeof(float) * (n6 * (n6 + 1) + n6 + ACC_WAVES * n6 + 4);
   const size_t solve_lds = sizeof(float) * ((n6 + 1) * (size_t)solve_ld((int)n6) + 72 * (size_t)N + n6 + 4);
   const bool use_reg = N <= 16;
-  const AccCfg cfg = acc_cfg(N);
-  const size_t acc_lds_used = use_reg ? acc_reg_lds_bytes(N, cfg) : acc_lds;
-  acc_fn_t acc_fn = use_reg ? acc_reg_fn(N, cfg) : k_ba_accumulate;
+  const size_t acc_lds_used = use_reg ? acc_reg_lds_bytes(N) : acc_lds;
+  acc_fn_t acc_fn = use_reg ? acc_reg_fn(N) : k_ba_accumulate;
   if (acc_lds_used > 64 * 1024 || solve_lds > 64 * 1024) {
     if (hipFuncSetAttribute((const void*)acc_fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)acc_lds_used) != hipSuccess ||
         hipFuncSetAttribute((const void*)ba_solve_fn(N), hipFuncAttributeMaxDynamicSharedMemorySize, (int)solve_lds) != hipSuccess) {
@@ -3193,11 +2937,10 @@ int devo_ba_solve_terms(const float* terms, const float* lmbda, const int64_t* i
       return DEVO_ERR_LAUNCH;
     }
   }
-  static const bool schur_inline = getenv("DEVO_BA_SCHUR_INLINE") != nullptr;
-  const bool defer = !use_reg && N > 0 && !schur_inline;
+  const bool defer = !use_reg && N > 0;                          // (the general kernel: the Schur term afterwards, see ba_forward_impl)
   // (poses / patches / intrinsics / weight are not read in terms mode; lmbda doubles as the 4-float intrinsics read)
   const TargetSrc src{nullptr, nullptr, 0, 0, 0, terms};
-  hipLaunchKernelGGL(acc_fn, dim3(L.n_part), dim3(use_reg ? cfg.waves * 64 : ACC_THREADS), acc_lds_used, st, (const float*)nullptr, (const float*)nullptr,
+  hipLaunchKernelGGL(acc_fn, dim3(L.n_part), dim3(use_reg ? acc_waves(N) * 64 : ACC_THREADS), acc_lds_used, st, (const float*)nullptr, (const float*)nullptr,
                      (const float*)(w + L.y) /* 4 readable floats */, src, (const float*)nullptr, lmbda, ii, jj, kk, (int*)(w + L.perm_b), (int*)(w + L.counts),
                      meta, 3, t0, N, (float*)(w + L.partials), patch_rec, patch_col, defer ? 1 << 16 : 0, ba_sig(E, N), L.max_seg);
   if ((rc = check_launch("devo_ba_solve_terms(accumulate)"))) return rc;
@@ -3205,7 +2948,7 @@ int devo_ba_solve_terms(const float* terms, const float* lmbda, const int64_t* i
     hipLaunchKernelGGL(k_ba_reduce, dim3((unsigned)((N * (N + 1) / 2 * 36 + n6 + 63) / 64)), dim3(512), 0, st, (float*)(w + L.partials), L.n_part, N, S,
                        (float*)(w + L.y), defer ? BA_EP_DEFERRED : ep);
     if (defer) ba_deferred_schur(st, patch_rec, patch_col, meta, N, L.max_seg, S, ep, (float*)(w + L.partials), L.partials_bytes);
-    hipLaunchKernelGGL(ba_solve_fn(N), dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, (float*)(w + L.y), N, dX, meta, 0, status_flag, 0);
+    hipLaunchKernelGGL(ba_solve_fn(N), dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, (float*)(w + L.y), N, dX, meta, 0, status_flag);
     if ((rc = check_launch("devo_ba_solve_terms(solve)"))) return rc;
   }
   hipLaunchKernelGGL(k_bt_dz, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024)), dim3(256), 0, st, dX, patch_rec, patch_col, (int*)(w + L.kx), meta, N, dZ_out,
@@ -3236,7 +2979,7 @@ int devo_ba_solve_terms_backward(const float* terms, const int64_t* ii, const in
     if (hipMemcpyAsync(rhs, g_dX, sizeof(float) * n6, hipMemcpyDeviceToDevice, st) != hipSuccess) { set_error("devo_ba_solve_terms_backward: copy failed"); return DEVO_ERR_LAUNCH; }
     hipLaunchKernelGGL(k_bt_rhs, dim3(64), dim3(256), 0, st, rhs, g_dZ, patch_rec, patch_col, kx, meta, N);
     const size_t solve_lds = sizeof(float) * ((n6 + 1) * (size_t)solve_ld((int)n6) + 72 * (size_t)N + n6 + 4);
-    hipLaunchKernelGGL(ba_solve_fn(N), dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, (float*)(w + L.y), N, ybar, meta, 0, (int*)nullptr, 0);
+    hipLaunchKernelGGL(ba_solve_fn(N), dim3(1), dim3(SOLVE_THREADS), solve_lds, st, S, (float*)(w + L.y), N, ybar, meta, 0, (int*)nullptr);
     if ((rc = check_launch("devo_ba_solve_terms_backward(solve)"))) return rc;
   }
   hipLaunchKernelGGL(k_bt_patch, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024)), dim3(256), 0, st, dX, ybar, g_dZ, patch_rec, patch_col, kx, meta, N, prec);
@@ -3439,7 +3182,7 @@ int devo_transform(const float* poses, const float* patches, const float* intrin
     }
     pm = CorrPlanMode{plan_width, plan_l1, 16 * corr_region_tmax(plan_radius), (int)nbins - 1};
   }
-  static const int tblock = [] { const char* e = getenv("DEVO_TRANSFORM_BLOCK"); const int v = e ? atoi(e) : 0; return (v == 64 || v == 128 || v == 256) ? v : 64; }();   // (tuning switch; 64 / 128 / 256 threads: 7.40 / 7.78 / 8.28 us at cfg2)
+  constexpr int tblock = 64;                                      // (64 / 128 / 256 threads: 7.40 / 7.78 / 8.28 us at cfg2)
   hipLaunchKernelGGL(P == 3 ? k_transform<true> : k_transform<false>, dim3(blocks_for(E, tblock, 4096)), dim3(tblock), 0, (hipStream_t)stream, poses, patches, intrinsics, ii, jj,
                      kk, coords_pp2, coords_2pp, valid, Ji, Jj, Jz, E, P, flags, plan ? plan + E + 1 : nullptr, plan_frames, plan_height,
                      nb, 2 * plan_radius + 2, plan_radius <= 3 ? 1 : 3, pm);

@@ -13,7 +13,6 @@
 #include "corr_plan.h"
 #include <hip/hip_fp16.h>
 #include <stdlib.h>
-#include <vector>
 #include <algorithm>
 #include <type_traits>
 
@@ -38,22 +37,9 @@ template <> __device__ __forceinline__ double from_f32<double>(float v) { return
 template <typename T> struct AccOf { typedef float type; };
 template <> struct AccOf<double> { typedef double type; };
 
-// output stores bypass the caches' allocation (written once, read by a later kernel)
 // Output stores: plain write-back stores.  Rounds 1-2 streamed them (nontemporal: "keep the L2 for feature rows"); measured in round 3
 // (profiles/r03_store_policy.txt): the streaming form writes every partially covered 32-byte sector on its own — 95.9 MB per cfg2 launch for
 // 76.2 MB of output — while write-back stores merge an edge's consecutive 216-byte rounds in the L2: 75.2 MB, and the lookup is 3 % faster.
-// DEVO_CORR_NT_STORES (A/B builds, tools/build_variant.sh) brings the streaming form back.
-#ifdef DEVO_CORR_NT_STORES
-__device__ __forceinline__ void store_streamed(float* p, float v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_streamed(double* p, double v) { __builtin_nontemporal_store(v, p); }
-__device__ __forceinline__ void store_streamed(__half* p, __half v) {
-  __builtin_nontemporal_store(__half_as_ushort(v), reinterpret_cast<unsigned short*>(p));
-}
-#else
-__device__ __forceinline__ void store_streamed(float* p, float v) { *p = v; }
-__device__ __forceinline__ void store_streamed(double* p, double v) { *p = v; }
-__device__ __forceinline__ void store_streamed(__half* p, __half v) { *p = v; }
-#endif
 
 __device__ __forceinline__ int floor_to_int(float v) { return corr_floor_to_int(v); }
 
@@ -179,8 +165,7 @@ template <typename T, int NG, int RMAX>
 __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
     const T* __restrict__ fmap1, CorrLevel lv0, CorrLevel lv1, int nlev, const float* __restrict__ coords,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, T* __restrict__ out, int BE, int E, int Np, int n2,
-    int C, int64_t out_estride, int64_t out_lstride, int R, const int* __restrict__ order,
-    unsigned long long* __restrict__ trace) {
+    int C, int64_t out_estride, int64_t out_lstride, int R, const int* __restrict__ order) {
   const int lvl = (nlev == 2) ? ((blockIdx.x >> 3) & 1) : 0;                      // wave-uniform
   const int gid = (nlev == 2) ? (((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) : blockIdx.x;
   const int nitems = (nlev == 2) ? (gridDim.x >> 1) : gridDim.x;                    // workgroups of this level
@@ -220,7 +205,6 @@ __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
     slot = start + (gid >> 3) - heavy_on(xcd);
   }
   if (slot >= BE) return;                                   // wave-uniform; no barriers in this kernel
-  const unsigned long long t_start = trace ? __builtin_readcyclecounter() : 0ULL;
   const int be = order ? order[slot] : slot;
   float* tile = s_tile + wave * WAVE_FLOATS;
   float* f1t = tile + F2_FLOATS;
@@ -235,8 +219,6 @@ __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
     px = coords[((int64_t)be * 2 + 0) * PP + lane] / coord_div;
     py = coords[((int64_t)be * 2 + 1) * PP + lane] / coord_div;
   }
-  unsigned long long t_geo = 0, t_first = 0, t_loop = 0;
-  if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_geo = __builtin_readcyclecounter(); }
   const int my_ox = floor_to_int(px) - R, my_oy = floor_to_int(py) - R;
   const float my_dx = px - floorf(px), my_dy = py - floorf(py);
   int ox[PP], oy[PP];
@@ -358,7 +340,6 @@ __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
     for (int j = 0; j < F1N; j++) raw1[j] = from_f32<T>(0.0f);
     int64_t koff = 0;
     fetch(koff, 0);
-    if (trace && sp == 0) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_first = __builtin_readcyclecounter(); }
 
     // registers -> LDS (as fp32), then the next chunk's loads are issued so that they fly under the FMAs
     auto stage = [&](int kc) {
@@ -410,7 +391,6 @@ __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
   }
   // ---- raw windows [p][a][c] (row stride D*D+1: conflict-free epilogue reads); they overwrite the dead box tile
   wave_lds_fence();
-  if (trace) t_loop = __builtin_readcyclecounter();
 #pragma unroll
   for (int g = 0; g < NG; g++) {
     if (lane + 64 * g < ntap) {
@@ -433,19 +413,13 @@ __global__ __launch_bounds__(WPB * 64) void corr_fwd_cl_kernel(
       const float dxp = __shfl(my_dx, p), dyp = __shfl(my_dy, p);
       if (l0 + lane < total) {
         const float* r = rawwin + p * (D * D + 1) + a * D + cx;
-        store_streamed(op, from_f32<T>(blend4(dxp, dyp, r[0], r[1], r[D], r[D + 1])));      // keep the L2 for feature rows
+        *op = from_f32<T>(blend4(dxp, dyp, r[0], r[1], r[D], r[D + 1]));
       }
       op += ostep;
       p += 1; a += 7;
       if (p >= PP) { p -= PP; a += 1; }
       while (a >= Dm) { a -= Dm; cx += 1; }
     }
-  }
-  if (trace && lane == 0) {                          // debug: per-wave (start, end, box size, hw id)
-    unsigned long long* t = trace + ((size_t)lvl * BE + slot) * 8;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    t[0] = t_start; t[1] = __builtin_readcyclecounter(); t[2] = (unsigned long long)npos_ll; t[3] = blockIdx.x;
-    t[4] = t_geo; t[5] = t_first; t[6] = t_loop;
   }
 }
 
@@ -545,14 +519,10 @@ __global__ __launch_bounds__(NT) void corr_bwd_kernel(
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const float* __restrict__ grad,
     float* __restrict__ d1, float* __restrict__ d2, int E, int Np, int n2, int C, int H2, int W2, int64_t s_b,
     int64_t s_n, int64_t s_c, int64_t s_h, int64_t s_w, int R, float* __restrict__ gs, BwdMeta* __restrict__ meta,
-    int* __restrict__ lists, int* __restrict__ cursors, int cap, unsigned long long* __restrict__ trace) {
+    int* __restrict__ lists, int* __restrict__ cursors, int cap) {
   // One workgroup per edge.  Every dependent memory round trip of this kernel costs ~4 k cycles under load (all workgroups are
   // resident at once), so the phases are ordered for few of them: (1) coordinates + indices, (2) gradient block + patch features
   // together, then LDS only until the feature rows, which are requested 8 at a time, one step ahead of their use.
-  unsigned long long t_prev = trace ? __builtin_readcyclecounter() : 0ull;
-  auto stamp = [&](int ph) {                                  // debug (DEVO_CORR_BWD_TRACE): cycles of phase ph, thread 0 of every workgroup
-    if (trace && threadIdx.x == 0) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); const unsigned long long t = __builtin_readcyclecounter(); trace[(size_t)blockIdx.x * 8 + ph] = t - t_prev; t_prev = __builtin_readcyclecounter(); }
-  };
   constexpr int DMX = 2 * RMAX + 2;
   __shared__ float s_g[PP * DMX * DMX];     // gradient of the raw D x D windows (correlation_kernel.cu:259-269)
   __shared__ float s_grad[(DMX - 1) * (DMX - 1) * PP];
@@ -590,7 +560,6 @@ __global__ __launch_bounds__(NT) void corr_bwd_kernel(
     for (int i = 0; i < GIT; i++) if (tid + i * NT < ng) s_grad[tid + i * NT] = gl[i];
   }
   __syncthreads();
-  stamp(0);
   {
     const float inv_dd = __builtin_amdgcn_rcpf((float)(D * D)), inv_d = __builtin_amdgcn_rcpf((float)D);
     for (int o = tid; o < PP * D * D; o += NT) {
@@ -611,7 +580,6 @@ __global__ __launch_bounds__(NT) void corr_bwd_kernel(
     }
   }
   __syncthreads();
-  stamp(1);
 
   int xmin = s_ox[0], xmax = s_ox[0], ymin = s_oy[0], ymax = s_oy[0];
 #pragma unroll
@@ -677,7 +645,6 @@ __global__ __launch_bounds__(NT) void corr_bwd_kernel(
         }
       }
     }
-    stamp(2);
     if (live) {
 #pragma unroll
       for (int p = 0; p < PP; p++) atomicAdd(g1 + k * PP + p, acc[p]);
@@ -695,7 +662,6 @@ __global__ __launch_bounds__(NT) void corr_bwd_kernel(
       if (x1 > x0 && y1 > y0) lists[(int64_t)m.frame * cap + atomicAdd(&cursors[m.frame], 1)] = be;      // (order: whoever comes first)
     }
   }
-  stamp(3);
 }
 
 // d_fmap2 of the segment-reduced backward: ONE workgroup owns a tile (frame, band of BH rows, slab of 16 channels) of the
@@ -976,19 +942,13 @@ static int launch_staged(const void* fmap1, const CorrLevel& lv0, const CorrLeve
   }
   const unsigned per_level = (nlev == 2) ? (unsigned)((BE + 7) / 8 * 8) : (unsigned)BE;      // whole groups of 8 alternate
   dim3 grid(per_level * nlev), block(WPB * 64);
-  static const bool force4 = getenv("DEVO_CORR_NP4") != nullptr;      // debug switch: run the r > 3 instantiation
-  unsigned long long* trace = nullptr;                                // debug switch: per-wave cycle stamps to stderr
-  const bool do_trace = getenv("DEVO_CORR_TRACE") != nullptr;
-  const size_t nrec = (size_t)BE * nlev;
-  if (do_trace) { (void)hipMalloc(&trace, nrec * 64); (void)hipMemset(trace, 0, nrec * 64); }
   const bool mfma = lv0.mfma_ok && (nlev == 1 || lv1.mfma_ok);
   corr_note_path(mfma ? CORR_PATH_MFMA4 : CORR_PATH_STAGED, BE, "channel count / alignment outside the matrix-core kernels, or DEVO_CORR_MFMA=0");
   if (mfma) {                                                         // matrix-core kernel (corr_mfma.h)
-    static const char* split_env = getenv("DEVO_CORR_SPLIT_LEVELS");  // debug: fused lookups as two sets of workgroups
-    const bool both = nlev == 2 && !(split_env && split_env[0] == '1') && !do_trace;
+    const bool both = nlev == 2;
     typedef typename std::conditional<std::is_same<T, double>::value, float, T>::type MT;   // (never fp64: mfma_ok is false)
     typedef void (*mfma_fn_t)(const MT*, CorrLevel, CorrLevel, int, const float*, const int64_t*, const int64_t*, MT*, int, int,
-                              int, int, int, int64_t, int64_t, int, const int*, unsigned long long*, int);
+                              int, int, int, int64_t, int64_t, int, const int*, int);
     // steps of 16 (fp32) / 32 (fp16) channels per pass, 4 or 8 of them (16 would not fit the patch into the registers):
     // C = 64 / 128 (fp32), 128 / 256 (fp16)
     constexpr int SC = sizeof(MT) == 2 ? 32 : 16;
@@ -997,60 +957,20 @@ static int launch_staged(const void* fmap1, const CorrLevel& lv0, const CorrLeve
                                   : (R <= 3 ? corr_fwd_mfma_kernel<MT, 3, NGR, 1> : corr_fwd_mfma_kernel<MT, 5, NGR, 1>))
     const mfma_fn_t fn = ngr == 4 ? DEVO_MFMA_PICK(4) : DEVO_MFMA_PICK(8);
 #undef DEVO_MFMA_PICK
-    // DEVO_MFMA_EPW edges (waves) per workgroup; grids are whole groups of 8 workgroups (one per XCD)
-    const unsigned wg_level = (unsigned)(((BE + DEVO_MFMA_EPW - 1) / DEVO_MFMA_EPW + 7) / 8 * 8);
-    const dim3 mgrid(DEVO_MFMA_EPW == 1 ? (both ? (unsigned)BE : per_level * nlev) : (both || nlev == 1 ? wg_level : wg_level * 2)), mblock(64 * DEVO_MFMA_EPW);
-    // Waves per CU: the kernel's registers allow 16.  Every resident wave streams its edge's boxes through the XCD's 4 MB L2, and
-    // plan neighbours share them: when the boxes of all resident waves together overrun the L2 (large radius, dense patch graph:
-    // BASELINE's stress configuration) the shared lines are evicted before the neighbour asks for them and the kernel becomes
-    // HBM-bound on re-reads.  An unused dynamic LDS allocation caps the resident waves (DEVO_MFMA_WAVES_PER_CU overrides).
-    size_t occ_pad = 0;
-    {
-      static const char* occ_env = getenv("DEVO_MFMA_WAVES_PER_CU");
-      int occ = occ_env ? atoi(occ_env) : 0;
-      if (occ > 0 && occ < 16) {
-        const size_t per_wg = (size_t)(160 * 1024) / (size_t)occ;
-        const size_t stat = 10 * 1024;                                   // (static LDS of one wave's workgroup, rounded up)
-        occ_pad = per_wg > stat + 512 ? ((per_wg - stat) / 512) * 512 : 0;
-        if (occ_pad > 64 * 1024 - stat) {
-          if (hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)occ_pad) != hipSuccess) { (void)hipGetLastError(); occ_pad = 64 * 1024 - stat; }
-        }
-      }
-    }
-    hipLaunchKernelGGL(fn, mgrid, mblock, occ_pad, st, (const MT*)fmap1, lv0, lv1, nlev, coords, ii, jj, (MT*)out, (int)BE, E, Np, n2,
-                       C, oes, ols, R, order, trace, 0);
+    // one edge (wave) per workgroup; the levels of an unfused lookup alternate in groups of 8 workgroups (one per XCD)
+    const dim3 mgrid(both ? (unsigned)BE : per_level * nlev), mblock(64 * MFMA_EPW);
+    hipLaunchKernelGGL(fn, mgrid, mblock, 0, st, (const MT*)fmap1, lv0, lv1, nlev, coords, ii, jj, (MT*)out, (int)BE, E, Np, n2,
+                       C, oes, ols, R, order, 0);
   } else
   if (!(lv0.staged_ok && (nlev == 1 || lv1.staged_ok))) {
     set_error("devo_corr_forward: this channel-blocked layout is only readable by the matrix-core kernel (fp32: C = 64 / 128, fp16: C = 128 / 256)");
-    if (trace) (void)hipFree(trace);
     return DEVO_ERR_UNSUPPORTED;
-  } else if (R <= 3 && !force4)   // (the <3,5> instantiation has room for every supported radius)
+  } else if (R <= 3)   // (the <3,5> instantiation has room for every supported radius)
     hipLaunchKernelGGL((corr_fwd_cl_kernel<T, 1, 3>), grid, block, 0, st, (const T*)fmap1, lv0, lv1, nlev, coords, ii, jj,
-                       (T*)out, (int)BE, E, Np, n2, C, oes, ols, R, order, trace);
+                       (T*)out, (int)BE, E, Np, n2, C, oes, ols, R, order);
   else
     hipLaunchKernelGGL((corr_fwd_cl_kernel<T, 3, 5>), grid, block, 0, st, (const T*)fmap1, lv0, lv1, nlev, coords, ii, jj,
-                       (T*)out, (int)BE, E, Np, n2, C, oes, ols, R, order, trace);
-  if (do_trace) {
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h(nrec * 8);
-    (void)hipMemcpy(h.data(), trace, nrec * 64, hipMemcpyDeviceToHost);
-    for (int l = 0; l < nlev; l++) {
-      double ph[4] = {0, 0, 0, 0}, sum = 0, mx = 0;
-      long cnt = 0;
-      for (long long i = 0; i < BE; i++) {
-        const unsigned long long* t = &h[((size_t)l * BE + i) * 8];
-        if (!t[1]) continue;
-        ph[0] += (double)(t[4] - t[0]); ph[1] += (double)(t[5] - t[4]); ph[2] += (double)(t[6] - t[5]); ph[3] += (double)(t[1] - t[6]);
-        const double d = (double)(t[1] - t[0]);
-        sum += d; if (d > mx) mx = d;
-        cnt++;
-      }
-      if (!cnt) cnt = 1;
-      fprintf(stderr, "[corr trace] level slot %d: wave mean %.0f max %.0f cycles; phase means: geometry %.0f, first chunk %.0f, channel loop %.0f, epilogue %.0f\n",
-              l, sum / cnt, mx, ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt);
-    }
-    (void)hipFree(trace);
-  }
+                       (T*)out, (int)BE, E, Np, n2, C, oes, ols, R, order);
   return check_launch("devo_corr_forward");
 }
 
@@ -1071,7 +991,7 @@ static int launch_mm(const void* fmap1_t, const CorrLevel& lv0, const CorrLevel&
                      const int* order, hipStream_t st, int order_kind = 0) {
   typedef typename std::conditional<std::is_same<T, double>::value, float, T>::type MT;
   typedef void (*mm_fn_t)(const MT*, CorrLevel, CorrLevel, int, const float*, const int64_t*, const int64_t*, MT*, int, int, int, int, int,
-                          int64_t, int64_t, int, const int*, int, unsigned long long*, const int*, MmGroupArgs);
+                          int64_t, int64_t, int, const int*, int, const int*, MmGroupArgs);
   // fp32: the patch operand's scale exponents sit behind its records (devo_corr_patch_operand_bytes)
   const int* exp1 = sizeof(MT) == 4 ? reinterpret_cast<const int*>(static_cast<const char*>(fmap1_t) + (size_t)(BE / E) * Np * C * PP * 4) : nullptr;
   const int nks = C / 32;
@@ -1096,7 +1016,7 @@ static int launch_mm(const void* fmap1_t, const CorrLevel& lv0, const CorrLevel&
       constexpr int NWG = sizeof(MT) == 2 ? 16 : 8;                  // waves per workgroup: what the registers allow per CU (one workgroup per CU: the region)
       mm_fn_t gfn = corr_fwd_mm_kernel<MT, 3, 4, 2, 3, NWG>;
       // per wave: result area + geometry records (the kernel's WAVE_LDS)
-      constexpr int cap = sizeof(MT) == 4 ? 128 : DEVO_MM_CAP;       // (the kernel's CAP)
+      constexpr int cap = sizeof(MT) == 4 ? 128 : MM_CAP;            // (the kernel's CAP)
       constexpr int rw_floats = (PP * (8 * 8 + 1) + 3) / 4 * 4 > PP * (cap + 4) ? (PP * (8 * 8 + 1) + 3) / 4 * 4 : PP * (cap + 4);
       constexpr int wave_lds = rw_floats * 4 + 2 * 16 * 4 * 4 + ((2 * PP * 2 * 4 + 15) / 16) * 16;
       const int lds = mm_region_bytes<MT>(128) + NWG * wave_lds;
@@ -1107,80 +1027,13 @@ static int launch_mm(const void* fmap1_t, const CorrLevel& lv0, const CorrLevel&
       const MmGroupArgs ga{order + 2 * BE + 2, (int)nbins, corr_grp_count(lv1.H2), corr_grp_count(lv1.W2)};
       const unsigned items = (unsigned)nbins * MM_ITEMS_PER_BIN;
       const unsigned gwg = (items + 7) / 8 * 8;
-      unsigned long long* gtrace = nullptr;                          // debug switch: per-wave 100 MHz stamps -> a schedule summary on stderr
-      if (getenv("DEVO_CORR_TRACE") != nullptr) { (void)hipMalloc(&gtrace, (size_t)gwg * NWG * 64); (void)hipMemset(gtrace, 0, (size_t)gwg * NWG * 64); }
       hipLaunchKernelGGL(gfn, dim3(gwg), dim3(64 * NWG), lds, st, (const MT*)fmap1_t, lv0, lv1, nlev, coords, ii, jj, (MT*)out, (int)BE, E, Np, n2, C,
-                         oes, ols, R, order, 0, gtrace, exp1, ga);
-      if (gtrace) {
-        (void)hipDeviceSynchronize();
-        std::vector<unsigned long long> h((size_t)gwg * NWG * 8);
-        (void)hipMemcpy(h.data(), gtrace, h.size() * 8, hipMemcpyDeviceToHost);
-        unsigned long long t0 = ~0ull, t1 = 0;
-        for (size_t i = 0; i < (size_t)gwg * NWG; i++) if (h[i * 8 + 3]) { t0 = std::min(t0, h[i * 8]); t1 = std::max(t1, h[i * 8 + 3]); }
-        // per compute unit (XCC id, SE id, CU id of HW_ID): busy time = union of its workgroups' spans; items; edges
-        struct CuAcc { double busy = 0, first = 1e30, last = 0; int wgs = 0, live = 0, edges = 0; };
-        std::vector<CuAcc> cu(16 * 1024);
-        double live_span = 0, empty_span = 0, stage = 0, item = 0, tail = 0; long nlive = 0, nempty = 0;
-        for (unsigned g = 0; g < gwg; g++) {
-          unsigned long long a = ~0ull, b = 0, ready = 0, done_min = ~0ull, done_max = 0; int edges = 0; unsigned long long hw = 0;
-          for (int w = 0; w < NWG; w++) {
-            const unsigned long long* t = &h[((size_t)g * NWG + w) * 8];
-            if (!t[3]) continue;
-            a = std::min(a, t[0]); b = std::max(b, t[3]); ready = std::max(ready, t[1]); hw = t[4]; edges = (int)t[5];
-            if (t[2]) { done_min = std::min(done_min, t[2]); done_max = std::max(done_max, t[2]); }
-          }
-          if (!b) continue;
-          const unsigned key = (unsigned)(((hw >> 32) & 0xf) << 10 | ((hw >> 13) & 0x7) << 7 | ((hw >> 8) & 0xf) << 3 | 0) & 16383u;   // xcc | se | cu
-          CuAcc& c = cu[key];
-          c.busy += (double)(b - a); c.first = std::min(c.first, (double)a); c.last = std::max(c.last, (double)b); c.wgs++; c.edges += edges;
-          if (edges > 0) { c.live++; nlive++; live_span += (double)(b - a); if (ready) stage += (double)(ready - a); if (done_max) { item += (double)(done_max - a); tail += (double)(done_max - done_min); } }
-          else { nempty++; empty_span += (double)(b - a); }
-        }
-        int ncu = 0; double bsum = 0, bmax = 0, emax = 0, esum = 0, lmax = 0;
-        for (auto& c : cu) if (c.wgs) { ncu++; bsum += c.busy; bmax = std::max(bmax, c.busy); esum += c.edges; emax = std::max(emax, (double)c.edges); lmax = std::max(lmax, (double)c.live); }
-        fprintf(stderr, "[corr group trace] %u workgroups (%ld with an item, %ld without), kernel span %.1f us; compute units seen %d: busy mean %.1f max %.1f us, item edges mean %.1f max %.0f, "
-                "items max %.0f; per item: span %.1f us (region ready after %.1f, last wave leaves the item after %.1f, first-to-last wave %.1f); workgroup without item: %.2f us\n",
-                gwg, nlive, nempty, (double)(t1 - t0) * 0.01, ncu, ncu ? bsum / ncu * 0.01 : 0.0, bmax * 0.01, ncu ? esum / ncu : 0.0, emax, lmax,
-                nlive ? live_span / nlive * 0.01 : 0.0, nlive ? stage / nlive * 0.01 : 0.0, nlive ? item / nlive * 0.01 : 0.0, nlive ? tail / nlive * 0.01 : 0.0,
-                nempty ? empty_span / nempty * 0.01 : 0.0);
-        (void)hipFree(gtrace);
-      }
+                         oes, ols, R, order, 0, exp1, ga);
       return check_launch("devo_corr_forward_pyramid2 (dense-product kernel, group form)");
     }
   }
-  unsigned long long* trace = nullptr;                                // debug switch: per-wave cycle stamps to stderr
-  const bool do_trace = getenv("DEVO_CORR_TRACE") != nullptr;
-  if (do_trace) { (void)hipMalloc(&trace, (size_t)BE * 64); (void)hipMemset(trace, 0, (size_t)BE * 64); }
-  const unsigned nwg = DEVO_MM_EPW == 1 ? (unsigned)BE : (unsigned)(((BE + DEVO_MM_EPW - 1) / DEVO_MM_EPW + 7) / 8 * 8);   // whole groups of 8 (one per XCD)
-  // DEVO_CORR_LDS_PAD=<bytes> (tuning switch, round 6's bounded attempt on the stress size): unused dynamic LDS per one-wave workgroup, i.e. a
-  // cap on the edges resident per compute unit (160 KB / (6.5 KB + pad)) and with it on the footprint an XCD streams through its L2 at a time
-  static const int lds_pad = [] { const char* e = getenv("DEVO_CORR_LDS_PAD"); const int v = e ? atoi(e) : 0; return v > 0 && v <= 60 * 1024 ? v : 0; }();
-  hipLaunchKernelGGL(fn, dim3(nwg), dim3(64 * DEVO_MM_EPW), (size_t)lds_pad, st, (const MT*)fmap1_t, lv0, lv1, nlev, coords, ii, jj, (MT*)out, (int)BE, E, Np, n2, C,
-                     oes, ols, R, order, 0, trace, exp1, MmGroupArgs{nullptr, 0, 0, 0});
-  if (do_trace) {
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h((size_t)BE * 8);
-    (void)hipMemcpy(h.data(), trace, (size_t)BE * 64, hipMemcpyDeviceToHost);
-    double ph[4] = {0, 0, 0, 0}, sum = 0, mx = 0, tiles = 0;
-    unsigned long long tmin = ~0ull, tmax = 0;
-    long cnt = 0;
-    for (long long i = 0; i < BE; i++) {
-      const unsigned long long* t = &h[(size_t)i * 8];
-      if (!t[4]) continue;
-      for (int q = 0; q < 4; q++) ph[q] += (double)(t[q + 1] - t[q]);
-      const double d = (double)(t[4] - t[0]);
-      sum += d; if (d > mx) mx = d;
-      tiles += (double)(t[5] % 1000 + t[5] / 1000);
-      if (t[0] < tmin) tmin = t[0];
-      if (t[4] > tmax) tmax = t[4];
-      cnt++;
-    }
-    if (!cnt) cnt = 1;
-    fprintf(stderr, "[corr mm trace] %ld waves, kernel span %.0f cycles; wave mean %.0f max %.0f cycles; phase means: plan slot + indices + coordinates %.0f, "
-            "geometry + patch operand + first tiles %.0f, tile loop %.0f, epilogue %.0f; %.1f tiles per edge\n",
-            cnt, (double)(tmax - tmin), sum / cnt, mx, ph[0] / cnt, ph[1] / cnt, ph[2] / cnt, ph[3] / cnt, tiles / cnt);
-    (void)hipFree(trace);
-  }
+  hipLaunchKernelGGL(fn, dim3((unsigned)BE), dim3(64 * MM_EPW), 0, st, (const MT*)fmap1_t, lv0, lv1, nlev, coords, ii, jj, (MT*)out, (int)BE, E, Np, n2, C,
+                     oes, ols, R, order, 0, exp1, MmGroupArgs{nullptr, 0, 0, 0});
   return check_launch("devo_corr_forward_pyramid2 (dense-product kernel)");
 }
 
@@ -1430,20 +1283,6 @@ int devo_corr_backward(const void* fmap1, const void* fmap2, const float* coords
   }
   g_corr_bwd_path = product ? DEVO_CORR_BWD_PRODUCT : seg ? DEVO_CORR_BWD_SEGMENTS : DEVO_CORR_BWD_ATOMIC;
   if (BE == 0) return DEVO_OK;
-  unsigned long long* btrace = nullptr;                               // debug switch: phase cycles of the per-edge kernel to stderr
-  static const bool do_btrace = getenv("DEVO_CORR_BWD_TRACE") != nullptr;
-  if (do_btrace) { (void)hipMalloc(&btrace, (size_t)BE * 64); (void)hipMemset(btrace, 0, (size_t)BE * 64); }
-  auto dump_trace = [&]() {
-    if (!do_btrace) return;
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> hv((size_t)BE * 8);
-    (void)hipMemcpy(hv.data(), btrace, (size_t)BE * 64, hipMemcpyDeviceToHost);
-    double h[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    for (long long i = 0; i < BE; i++) for (int q = 0; q < 8; q++) h[q] += (double)hv[(size_t)i * 8 + q];
-    fprintf(stderr, "[corr bwd trace] per-edge kernel, mean cycles per workgroup: coordinates + gradient block + patch %.0f | window gradients %.0f | rows %.0f | patch atomics + hand-over %.0f\n",
-            (double)h[0] / BE, (double)h[1] / BE, (double)h[2] / BE, (double)h[3] / BE);
-    (void)hipFree(btrace);
-  };
   if (product) {
     char* scratch = reinterpret_cast<char*>(ws);
     const size_t pair_off = (gs_bytes + 15) & ~(size_t)15, f1t_off = pair_off + pair_bytes, cur_off = f1t_off + f1t_bytes;
@@ -1467,9 +1306,7 @@ int devo_corr_backward(const void* fmap1, const void* fmap2, const float* coords
       hipLaunchKernelGGL(corr_bwd_frame_kernel<4>, dim3((unsigned)(tiles_x * (C / 128)), (unsigned)((H2 + 7) / 8), (unsigned)frames), dim3(256), 0, st,
                          (const float*)f1t, (const float*)gs, (const BwdPair*)pairs, (const int*)cursors, (float*)fmap2_grad, n2, C, H2, W2, f2s[0], f2s[1], D,
                          (int)BE, tiles_x);
-    const int rc = check_launch("devo_corr_backward");
-    if (do_btrace) (void)hipFree(btrace);
-    return rc;
+    return check_launch("devo_corr_backward");
   }
   if (seg) {
     char* scratch = reinterpret_cast<char*>(ws);
@@ -1481,17 +1318,15 @@ int devo_corr_backward(const void* fmap1, const void* fmap2, const float* coords
     (void)hipMemsetAsync(cursors, 0, (size_t)frames * 4, st);
     hipLaunchKernelGGL((radius <= 3 ? corr_bwd_kernel<true, 3> : corr_bwd_kernel<true, 5>), dim3((unsigned)BE), dim3(NT), 0, st, (const float*)fmap1, (const float*)fmap2, coords, ii, jj,
                        grad, (float*)fmap1_grad, (float*)fmap2_grad, E, Np, n2, C, H2, W2, f2s[0], f2s[1], f2s[2], f2s[3], f2s[4], radius,
-                       gs, meta, lists, cursors, (int)BE, btrace);
+                       gs, meta, lists, cursors, (int)BE);
     hipLaunchKernelGGL(corr_bwd_tile_kernel, dim3((unsigned)(C / BWD_CS), (unsigned)((H2 + BH - 1) / BH), (unsigned)frames), dim3(BWD_THREADS),
                        tile_lds, st, (const float*)fmap1, gs, meta, lists, cursors, (float*)fmap2_grad, n2, C, H2, W2, f2s[0], f2s[1], f2s[3],
                        f2s[4], D, BH, (int)BE);
-    dump_trace();
     return check_launch("devo_corr_backward");
   }
   hipLaunchKernelGGL((radius <= 3 ? corr_bwd_kernel<false, 3> : corr_bwd_kernel<false, 5>), dim3((unsigned)BE), dim3(NT), 0, st, (const float*)fmap1,
                      (const float*)fmap2, coords, ii, jj, grad, (float*)fmap1_grad, (float*)fmap2_grad, E, Np, n2, C, H2,
-                     W2, f2s[0], f2s[1], f2s[2], f2s[3], f2s[4], radius, (float*)nullptr, (BwdMeta*)nullptr, (int*)nullptr, (int*)nullptr, 0, btrace);
-  dump_trace();
+                     W2, f2s[0], f2s[1], f2s[2], f2s[3], f2s[4], radius, (float*)nullptr, (BwdMeta*)nullptr, (int*)nullptr, (int*)nullptr, 0);
   return check_launch("devo_corr_backward");
 }
 

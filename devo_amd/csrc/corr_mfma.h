@@ -23,20 +23,14 @@
 // (torch.stack([c0, c1], -1)) as whole lines.
 #pragma once
 
-#ifndef DEVO_MFMA_RING
-#define DEVO_MFMA_RING 4
-#endif
-#ifndef DEVO_MFMA_WAVES
-#define DEVO_MFMA_WAVES 4
-#endif
+constexpr int MFMA_RING = 4;          // steps in the register ring (3 in flight ahead of the products)
+constexpr int MFMA_WAVES = 4;         // waves per SIMD
 // Edges (= waves) per workgroup.  The waves of a workgroup never synchronise; putting the waves of EPW CONSECUTIVE plan slots
 // into one workgroup only guarantees that spatial neighbours (the plan sorts by frame, 16-row band, 8-px column) run on the
 // same CU at the same time, so that their overlapping boxes could meet in the CU's L1.  Measured on cfg2 (profiles/README.md,
 // r02): 1 / 2 / 4 / 8 edges per workgroup = 191 / 208 / 211 / 222 us (fp32), 99 / 100 / 104 / 128 us (fp16) — the lost
-// heavy-first schedule and the coarser dispatch cost more than the shared lines save, so the default stays 1.
-#ifndef DEVO_MFMA_EPW
-#define DEVO_MFMA_EPW 1
-#endif
+// heavy-first schedule and the coarser dispatch cost more than the shared lines save, so it stays 1.
+constexpr int MFMA_EPW = 1;
 typedef float mfma_acc4 __attribute__((ext_vector_type(4)));
 typedef unsigned int v4u32 __attribute__((ext_vector_type(4)));
 typedef _Float16 mfma_h4 __attribute__((ext_vector_type(4)));
@@ -65,14 +59,13 @@ __device__ __forceinline__ int corr_plan_slot(const int* __restrict__ order, int
   acc2 = __builtin_amdgcn_mfma_f32_4x4x1f32(a2, (BV), acc2, 4, (U), 0)
 
 template <typename T, int RMAX, int NGR, int NL>   // NGR = C / (16 | 32) steps per pass (a multiple of the ring); NL = levels per wave
-__global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per_eu(DEVO_MFMA_WAVES, DEVO_MFMA_WAVES))) void corr_fwd_mfma_kernel(
+__global__ __launch_bounds__(64 * MFMA_EPW) __attribute__((amdgpu_waves_per_eu(MFMA_WAVES, MFMA_WAVES))) void corr_fwd_mfma_kernel(
     const T* __restrict__ fmap1, CorrLevel lv0, CorrLevel lv1, int nlev, const float* __restrict__ coords,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, T* __restrict__ out, int BE, int E, int Np, int n2,
-    int C, int64_t out_estride, int64_t out_lstride, int R, const int* __restrict__ order,
-    unsigned long long* __restrict__ trace, int heavy_only) {
+    int C, int64_t out_estride, int64_t out_lstride, int R, const int* __restrict__ order, int heavy_only) {
   // NL == 1 with nlev == 2: the levels alternate in groups of 8 workgroups (see corr_fwd_cl_kernel); NL == 2: one
   // workgroup per edge does both.  lev(l) = the level this wave works on as its l-th.
-  constexpr int EPW = DEVO_MFMA_EPW;
+  constexpr int EPW = MFMA_EPW;
   const int wv = EPW > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;      // this wave's edge inside the workgroup
   const int wlvl = (NL == 1 && nlev == 2) ? ((blockIdx.x >> 3) & 1) : 0;                      // wave-uniform
   const int wgid = (NL == 1 && nlev == 2) ? (((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) : blockIdx.x;
@@ -104,7 +97,6 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
     if (slot >= (order ? min(max(order[BE], 0), BE) : 0)) return;
   }
   if (slot >= BE) return;                     // wave-uniform; no workgroup barriers in this kernel
-  const unsigned long long t_start = trace ? __builtin_readcyclecounter() : 0ULL;
   const int be = order ? order[slot] : slot;
   const int D = 2 * R + 2, ntap = D * D;
   const int b = be / E, e = be - b * E;
@@ -125,8 +117,6 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
       asm("v_writelane_b32 %0, %1, %2" : "+v"(cpy) : "s"(cv[PP + p]), "n"(p));
     }
   }
-  unsigned long long t_geo = 0, t_first = 0, t_loop = 0;
-  if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_geo = __builtin_readcyclecounter(); }
   // scaled coordinates of the lane's pixel per level index.  coords / div is the reference's true division; for a power of
   // two (1 and 4 in DEVO) x * (1 / div) is the same correctly rounded value, and it spares ~12 vector instructions per
   // division (every vector instruction of this kernel competes with the MFMAs for the SIMD's issue slot).
@@ -271,7 +261,7 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
   // 16-byte piece q (4 channels) of step g starts at channel c = 16 g + 4 q: block c / cb, offset c % cb
   // (cb = 1 << cb_shift; channels-last = one block of all channels, cb_shift = 30)
   auto as_f4 = [](v4u32 v) -> float4 { float4 f; __builtin_memcpy(&f, &v, sizeof(f)); return f; };
-  constexpr int RING = DEVO_MFMA_RING;
+  constexpr int RING = MFMA_RING;
   float4 rb[RING][4];
   // Byte offset of piece q of step g = g * G16 + d[q]: linear in g for the layouts the launcher lets through (channel
   // blocks of 4, 8 or 16 channels, or channels-last), so a step costs 4 scalar adds besides its 4 loads.
@@ -300,7 +290,6 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
 #pragma unroll
     for (int g = 0; g < RING - 1; g++) { fetch(g, g % NGR, cur.off, r0, pc0); __builtin_amdgcn_sched_barrier(0); }
   }
-  if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_first = __builtin_readcyclecounter(); }
   for (int sg = 0; sg < nseg; sg++) {
     const int lc = seg_level(sg), ln = seg_level(min(sg + 1, nseg - 1));         // wave-uniform
     const __amdgpu_buffer_rsrc_t rsc = frame_rsrc(lc), rsn = frame_rsrc(ln);
@@ -362,7 +351,6 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
     nxt = position(sg + 2);
   }
   wave_lds_fence();
-  if (trace) t_loop = __builtin_readcyclecounter();
   // ---- fused bilinear blend + axis swap + output permutation (correlation_kernel.cu:221-232).
   //      Output element (l, t): level index l, t = q * 9 + p with q = cx * Dm + a (cx = x offset: permute(0,1,3,2,4,5),
   //      a = y offset), p = i0*3+j0, goes to  out[be * estride + t * lstride + offset(l)].  A lane keeps ITS (p, l) for the
@@ -398,7 +386,7 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
 #pragma clang fp contract(off)
           o = w00 * r[0]; o = o + w01 * r[1]; o = o + w10 * r[rstride]; o = o + w11 * r[rstride + 1];
         }
-        store_streamed(op, from_f32<T>(lvl_live ? o : 0.0f));
+        *op = from_f32<T>(lvl_live ? o : 0.0f);
       }
       op += ostep;
       q += GRPS; a += GRPS;
@@ -406,12 +394,6 @@ __global__ __launch_bounds__(64 * DEVO_MFMA_EPW) __attribute__((amdgpu_waves_per
       if (a >= Dm) { a -= Dm; cx += 1; }
       while (a >= Dm) { a -= Dm; cx += 1; }
     }
-  }
-  if (trace && lane == 0) {                          // debug: per-wave cycle stamps (see launch_staged)
-    unsigned long long* t = trace + ((size_t)wlvl * BE + slot) * 8;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    t[0] = t_start; t[1] = __builtin_readcyclecounter(); t[2] = (unsigned long long)g0.nslots; t[3] = blockIdx.x;
-    t[4] = t_geo; t[5] = t_first; t[6] = t_loop;
   }
 #undef LVF
 }

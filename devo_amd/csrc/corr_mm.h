@@ -27,28 +27,15 @@ typedef _Float16 mm_h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 mm_h2 __attribute__((ext_vector_type(2)));
 typedef float mm_f4 __attribute__((ext_vector_type(4)));
 
-#ifndef DEVO_MM_WAVES
-#define DEVO_MM_WAVES 4        // waves per SIMD, fp16 storage (128 registers)
-#endif
-#ifndef DEVO_MM_WAVES32
-#define DEVO_MM_WAVES32 2      // fp32 storage (the hi / lo patch, twice the bytes in flight, the held outputs: up to 200 registers; the kernel's time does not
-                               // depend on 2, 3 or 4 waves per SIMD: the texture addresser is the busy unit).  fp16, radius 4 - 5: one wave less
-#endif
+constexpr int MM_WAVES = 4;            // waves per SIMD, fp16 storage (128 registers)
+constexpr int MM_WAVES32 = 2;          // fp32 storage (the hi / lo patch, twice the bytes in flight, the held outputs: up to 200 registers; the kernel's time does not
+                                       // depend on 2, 3 or 4 waves per SIMD: the texture addresser is the busy unit).  fp16, radius 4 - 5: one wave less
 // Edges (= waves) per workgroup: EPW CONSECUTIVE plan slots — image neighbours — run on one CU at the same time, so that the lines their
-// boxes share can meet in the CU's 32 KB L1 instead of being fetched from the L2 once per edge.  DEVO_MM_SYNC = 1 additionally keeps the
-// waves of a workgroup on the same tile slot (one s_barrier per slot: ~60 cycles) — an L1 line lives about a thousand cycles.
-#ifndef DEVO_MM_EPW
-#define DEVO_MM_EPW 1
-#endif
-#ifndef DEVO_MM_RT16
-#define DEVO_MM_RT16 4          // fp16 storage: tiles in the register ring (3 in flight ahead of the products)
-#endif
-#ifndef DEVO_MM_ALIGN4
-#define DEVO_MM_ALIGN4 1        // fp16 storage: boxes start at a multiple of 4 positions and are a multiple of 4 wide: every quad of lanes reads inside ONE 128-byte line
-#endif
-#ifndef DEVO_MM_SYNC
-#define DEVO_MM_SYNC 0
-#endif
+// boxes share can meet in the CU's 32 KB L1 instead of being fetched from the L2 once per edge.  Measured no gain (as corr_mfma.h's): 1.
+constexpr int MM_EPW = 1;
+constexpr int MM_RT16 = 4;             // fp16 storage: tiles in the register ring (3 in flight ahead of the products)
+constexpr bool MM_ALIGN4 = true;       // fp16 storage: boxes start at a multiple of 4 positions and are a multiple of 4 wide: every quad of lanes reads inside ONE 128-byte line
+constexpr int MM_CAP = 160;            // result area of a box, radius <= 3 (positions)
 
 // fp32 operands are stored pre-split ("split" formats, written once per version of the tensor by devo_corr_patch_transpose /
 // devo_corr_pyramid_split): a value x of a group with scale exponent e (per patch / per frame, chosen so that the group's largest
@@ -181,32 +168,26 @@ __device__ __forceinline__ int mm_plan_slot(const int* __restrict__ order, int B
 // 1's tiles with ds_read_b128 from the region, a unit that was idle.  Edges whose level-1 box leaves the region (the plan sorts
 // them into the HEAVY class), heavy and dead edges keep the per-edge paths inside the same launch.
 struct MmGroupArgs { const int* starts; int nbins, ngy, ngx; };     // bin starts of the group plan (nbins + 1 entries), bins, groups per frame
-#ifndef DEVO_MM_ITEM_EDGES
-#define DEVO_MM_ITEM_EDGES (1 << 20)
-#endif
-#ifndef DEVO_MM_ITEMS_PER_BIN
-#define DEVO_MM_ITEMS_PER_BIN 1
-#endif
-constexpr int MM_ITEM_EDGES = DEVO_MM_ITEM_EDGES;      // an item = at most this many edges of one group (larger groups: several items, each staging the region)
-constexpr int MM_ITEMS_PER_BIN = DEVO_MM_ITEMS_PER_BIN;    // workgroups reserved per bin (the last one takes whatever is left)
+constexpr int MM_ITEM_EDGES = 1 << 20;      // an item = at most this many edges of one group (larger groups: several items, each staging the region)
+constexpr int MM_ITEMS_PER_BIN = 1;         // workgroups reserved per bin (the last one takes whatever is left)
 template <typename T> constexpr int mm_region_bytes(int C) {        // the staged region (radius 3), whole kilobytes (LDS-DMA writes 1 KB per instruction)
   return ((CORR_GRP_T + 2 * 3 + 3) * (CORR_GRP_T + 2 * 3 + 3) * C * (int)sizeof(T) + 1023) / 1024 * 1024;
 }
 
 template <typename T, int RMAX, int NKS, int NL, int RFIX, int NW = 1>   // NKS = C / 32 K steps per tile; NL = levels per wave; RFIX > 0: the radius is this constant
-__global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? DEVO_MM_WAVES - (RMAX > 3 ? 1 : 0) : DEVO_MM_WAVES32, sizeof(T) == 2 ? DEVO_MM_WAVES - (RMAX > 3 ? 1 : 0) : DEVO_MM_WAVES32))) void corr_fwd_mm_kernel(
+__global__ __launch_bounds__(64 * (NW > 1 ? NW : MM_EPW)) __attribute__((amdgpu_waves_per_eu(sizeof(T) == 2 ? MM_WAVES - (RMAX > 3 ? 1 : 0) : MM_WAVES32, sizeof(T) == 2 ? MM_WAVES - (RMAX > 3 ? 1 : 0) : MM_WAVES32))) void corr_fwd_mm_kernel(
     const T* __restrict__ fmap1_t, CorrLevel lv0, CorrLevel lv1, int nlev, const float* __restrict__ coords,
     const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, T* __restrict__ out, int BE, int E, int Np, int n2,
     int C, int64_t out_estride, int64_t out_lstride, int R_arg, const int* __restrict__ order, int heavy_only,
-    unsigned long long* __restrict__ trace, const int* __restrict__ exp1, MmGroupArgs grp) {
+    const int* __restrict__ exp1, MmGroupArgs grp) {
   constexpr bool LDS1 = NW > 1;
-  static_assert(!LDS1 || (NL == 2 && RFIX == 3 && RMAX == 3 && DEVO_MM_EPW == 1), "the group form: fused two-level lookups at radius 3");
+  static_assert(!LDS1 || (NL == 2 && RFIX == 3 && RMAX == 3 && MM_EPW == 1), "the group form: fused two-level lookups at radius 3");
   const int R = RFIX > 0 ? RFIX : R_arg;        // (DEVO's radius 3 and the stress configuration's 5 as constants: window sizes, loop bounds and
                                                 //  the epilogue's guards fold away)
   constexpr bool HALF = sizeof(T) == 2;
   constexpr unsigned ESZ = sizeof(T);
   constexpr int LPS = HALF ? 1 : 2;                 // 16-byte loads per lane and K step
-  constexpr int RT = HALF ? DEVO_MM_RT16 : 2;       // ring of tiles (RT - 1 tiles in flight ahead of the products)
+  constexpr int RT = HALF ? MM_RT16 : 2;            // ring of tiles (RT - 1 tiles in flight ahead of the products)
   const int wlvl = (NL == 1 && nlev == 2) ? ((blockIdx.x >> 3) & 1) : 0;                      // wave-uniform
   const int wgid = (NL == 1 && nlev == 2) ? (((blockIdx.x >> 4) << 3) | (blockIdx.x & 7)) : blockIdx.x;
   const int nwg = (NL == 1 && nlev == 2) ? (gridDim.x >> 1) : gridDim.x;
@@ -217,18 +198,15 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
   //   box layout  [p][BOXS]        slot s of pixel p at p * BOXS + s (boxes of <= CAP positions; BOXS = CAP + 4 so that the 8 lanes
   //                                of a ds_write_b128 group, 8 pixels x the same 4 slots, fall into different banks)
   //   raw windows [p][D*D + 1]     tap (a, c) of pixel p: window-by-window tiles (larger boxes)
-  constexpr bool ALIGN4 = DEVO_MM_ALIGN4 != 0 && sizeof(T) == 2;     // measured (profiles/r04_lookup_experiments.txt, 9): fp16 64 -> 60 us, fp32 120 -> 124
-#ifndef DEVO_MM_CAP
-#define DEVO_MM_CAP 160
-#endif
+  constexpr bool ALIGN4 = MM_ALIGN4 && sizeof(T) == 2;               // measured (profiles/r04_lookup_experiments.txt, 9): fp16 64 -> 60 us, fp32 120 -> 124
   // (a box beyond CAP positions walks the 9 windows one after the other — 36 tiles where a 12 x 12 box has 9: with CAP = 128, 6 % of cfg2's
   //  edges did, 18 % of all tiles)
-  constexpr int CAP = RMAX <= 3 ? ((LDS1 && !HALF) ? 128 : DEVO_MM_CAP) : 256;      // (fp32 group form: the region leaves 5.4 KB per wave)
+  constexpr int CAP = RMAX <= 3 ? ((LDS1 && !HALF) ? 128 : MM_CAP) : 256;           // (fp32 group form: the region leaves 5.4 KB per wave)
   static_assert(RMAX > 3 || (CAP % 16 == 0 && CAP >= 128 && CAP <= 192), "result area: 8 .. 12 tiles");
   constexpr int BOXS = CAP + 4;
   constexpr int RWIN_FLOATS = (PP * (DMAX * DMAX + 1) + 3) / 4 * 4;
   constexpr int RW_FLOATS = RWIN_FLOATS > PP * BOXS ? RWIN_FLOATS : PP * BOXS;
-  constexpr int EPW = DEVO_MM_EPW;
+  constexpr int EPW = MM_EPW;
   const int wv = (EPW > 1 || LDS1) ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0;      // this wave's edge inside the workgroup
   // per wave: ONE level's result area (a level is blended before the next one's tiles land) | per (level index, pixel): dx, dy, tap (0, 0)'s
   // index in the result area, row stride | window origins (window-by-window tiles only)
@@ -260,8 +238,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
   constexpr unsigned RPOS = 8u * ESZ;                     // bytes per position and 8-channel block (level 1 is stored in 8-channel blocks)
   constexpr unsigned RROW = GRP_RW * RPOS, RBLK = GRP_RW * GRP_RW * RPOS;
   int it_lo = 0, it_hi = 0, it_b = -1, it_f = -1, ry0 = 0, rx0 = 0, hv_n = 0, dd_n = 0;
-  unsigned long long g_st[4] = {0, 0, 0, 0};               // debug (DEVO_CORR_TRACE, group form): 100 MHz stamps of this wave: start, region ready, item done, end
-  if (LDS1 && trace) g_st[0] = __builtin_amdgcn_s_memrealtime();
   bool region_pending = false;                            // this wave still owes the workgroup's ONE barrier (after its share of the DMA has landed)
   if constexpr (LDS1) {
     const int per = ((int)gridDim.x + 7) >> 3;            // workgroup g runs on XCD g % 8: every XCD owns a contiguous range of items (= of bins = of frames)
@@ -279,11 +255,7 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
         ry0 = (g2 / grp.ngx) * CORR_GRP_T - 3 - 1; rx0 = (g2 % grp.ngx) * CORR_GRP_T - 3 - 1;
       }
     }
-#ifdef DEVO_MM_DBG_NOSTAGE    // timing experiment (wrong results): nothing is staged
-    if (false) {
-#else
     if (it_hi > it_lo && it_f >= 0) {
-#endif
       // the region [block][row][column][RPOS bytes], a verbatim copy of the level's blocks: chunk q = bytes q KB .. of it, 16 per lane;
       // rows / columns outside the frame and the bytes behind the region carry the out-of-range offset: the DMA writes zeros for them
       const T* base = static_cast<const T*>(lv1.fmap2) + (int64_t)it_b * lv1.s_b + (int64_t)it_f * lv1.s_n;
@@ -309,7 +281,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
         region_pending = false;
-        if (trace) g_st[1] = __builtin_amdgcn_s_memrealtime();
       }
     }
   };
@@ -334,15 +305,12 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
     if (idx < it_hi) { slot = idx; in_item = true; }
     else {
       region_ready();                          // (a wave without an edge of the item still owes the barrier)
-      if (trace && g_st[2] == 0) g_st[2] = __builtin_amdgcn_s_memrealtime();
       const int nturn = (it_hi - it_lo - wv + NW - 1) / NW;                     // turns this wave spent on the item (>= 0)
       const int h = ((int)blockIdx.x * NW + wv) + (turn - max(nturn, 0)) * (int)gridDim.x * NW;
       if (h >= hv_n + dd_n) break;
       slot = h < hv_n ? h : BE - dd_n + (h - hv_n);          // the HEAVY class in front of the plan, the DEAD one at its end
     }
   } else if (turn > 0) break;
-  unsigned long long t_st[5] = {0, 0, 0, 0, 0};  // debug (DEVO_CORR_TRACE): cycle stamps of this wave's phases
-  if (trace) t_st[0] = __builtin_readcyclecounter();
   const int be = order ? order[slot] : slot;
   const int D = 2 * R + 2, ntap = D * D;
   const int b = be / E, e = be - b * E;
@@ -377,7 +345,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
       }
     }
   }
-  if (trace) { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); t_st[1] = __builtin_readcyclecounter(); }
   float qx, qy;                               // coordinates at this lane's level: coords / div (the reference's true division)
   {
     auto pow2 = [](float d) -> bool { return (__float_as_uint(d) & 0x807fffffu) == 0u && d >= 1.0f; };
@@ -481,7 +448,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
     }
   }
   __builtin_amdgcn_sched_barrier(0);        // patch loads first: the loop's s_waitcnt counts assume they are the oldest
-  if (trace) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); t_st[2] = __builtin_readcyclecounter(); }
 
   v4u32 rb[RT][NKS][LPS];
   // the products of one tile (ring slot r) -> 16 positions x 16 columns of sums
@@ -585,13 +551,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
       const int gy = G.ymin + pyy, gx = G.xmin + (sl - __mul24(pyy, G.bw));
       const bool ok = sl < G.nslots && (unsigned)gy < (unsigned)LVF(l, H2) && (unsigned)gx < (unsigned)LVF(l, W2);
       const unsigned voff = ok ? (unsigned)gy * shb[l] + (unsigned)gx * swb[l] + lane_piece[l] : OFF_NONE;
-#ifdef DEVO_MM_DBG_NOL1      // timing experiment (wrong results): level index 1's tiles are not fetched at all (what a level read from LDS would leave of the addresser's time)
-      if (l == 1) {
-#pragma unroll
-        for (int s = 0; s < NKS; s++) { xr[ring][s][0] = v4u32{voff, voff ^ (unsigned)s, voff, voff}; if constexpr (!HALF) xr[ring][s][1] = v4u32{voff, voff, voff ^ (unsigned)s, voff}; }
-        return;
-      }
-#endif
 #pragma unroll
       for (int s = 0; s < NKS; s++) {
         xr[ring][s][0] = __builtin_amdgcn_raw_buffer_load_b128(rsl[l], voff, (unsigned)s * step_b[l], 0);
@@ -643,9 +602,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
     if constexpr (LDS1)
       from_lds = in_item && it_f >= 0 && b == it_b && (int)fj == it_f && lv1.cb_shift == 3 && g1.ntile > 0 && g1.xmin >= rx0 && g1.ymin >= ry0 &&
                  g1.xmin + g1.bw <= rx0 + GRP_RW && g1.ymin + g1.bh <= ry0 + GRP_RW;
-#ifdef DEVO_MM_DBG_NOLDS     // timing experiment: the group form's schedule with level index 1 through the addresser
-    from_lds = false;
-#endif
     using std::integral_constant;
     auto zero_area = [&]() { for (int i = lane; i < PP * BOXS; i += 64) s_rawwin[i] = 0.0f; };
     const int k0 = g0.ntile, k1 = NL == 2 ? g1.ntile : 0;
@@ -739,11 +695,7 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
       const int sl = t * 16 + mi;
       const int pyy = (int)((fmi + (float)(t * 16)) * S.inv_bw);      // exact: sl < 2^16, error margin 0.5 / bw
       const int gy = S.ymin + pyy, gx = S.xmin + (sl - __mul24(pyy, S.bw));
-#ifdef DEVO_MM_DBG_FRAC      // timing experiment (wrong results): fetch only DEVO_MM_DBG_FRAC / 8 of every box
-      const bool ok = tt < ntotp && sl < (S.nslots * DEVO_MM_DBG_FRAC) / 8 && (unsigned)gy < (unsigned)S.H2 && (unsigned)gx < (unsigned)S.W2;
-#else
       const bool ok = tt < ntotp && sl < S.nslots && (unsigned)gy < (unsigned)S.H2 && (unsigned)gx < (unsigned)S.W2;
-#endif
       const unsigned voff = ok ? (unsigned)gy * S.shb + (unsigned)gx * S.swb + (l1 ? lane_piece[NL - 1] : lane_piece[0]) : OFF_NONE;
 #pragma unroll
       for (int s = 0; s < NKS; s++) {
@@ -831,7 +783,6 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
       blend(l);
     }
   }
-  if (trace) { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); t_st[3] = __builtin_readcyclecounter(); }
   // ---- stores: lane (a, p) owns outputs (cx, a, p) of every level index
   {
     T* const rec = out + (int64_t)be * out_estride;
@@ -856,28 +807,14 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : DEVO_MM_EPW)) __attribute__((am
             } else {
 #pragma unroll
               for (int l = 0; l < NL; l++)
-                store_streamed(rec + (int64_t)(t0 + cx * (Dm * PP)) * out_lstride + LVF(l, out_offset), from_f32<T>(held[l][rd][cx]));
+                rec[(int64_t)(t0 + cx * (Dm * PP)) * out_lstride + LVF(l, out_offset)] = from_f32<T>(held[l][rd][cx]);
             }
           }
         }
       }
     }
   }
-  if (!LDS1 && trace && lane == 0) {                 // per-wave cycle stamps (launch_mm prints the phase means)
-    unsigned long long* t = trace + (size_t)slot * 8;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    t[0] = t_st[0]; t[1] = t_st[1]; t[2] = t_st[2]; t[3] = t_st[3]; t[4] = __builtin_readcyclecounter(); t[5] = (unsigned long long)(nt0 + 1000 * (ntot - nt0));
-  }
   if constexpr (LDS1) wave_lds_fence();                    // (the next edge's records overwrite this one's result area / geometry)
   }   // turns
-  if (LDS1 && trace && lane == 0) {
-    unsigned long long* t = trace + ((size_t)blockIdx.x * NW + wv) * 8;
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    unsigned xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    t[0] = g_st[0]; t[1] = g_st[1]; t[2] = g_st[2]; t[3] = __builtin_amdgcn_s_memrealtime();
-    t[4] = (unsigned long long)hw | ((unsigned long long)(xcc & 0xf) << 32); t[5] = (unsigned long long)max(it_hi - it_lo, 0);
-  }
 #undef LVF
 }

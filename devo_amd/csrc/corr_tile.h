@@ -3,11 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#ifndef DEVO_PLAN_BAND
-#define DEVO_PLAN_BAND 16                        // rows per band of the locality plan
-#endif
-
 namespace devo {
+
+constexpr int CORR_PLAN_BAND = 16;               // rows per band of the locality plan
 
 constexpr int CORR_KC = 8;                       // channels staged per LDS chunk
 constexpr int CORR_ROWPAD = CORR_KC + 4;         // LDS row stride of a staged position in floats
@@ -26,12 +24,9 @@ __host__ __device__ __forceinline__ bool tile_fits(int w, int h, int ng) {
 }
 
 
-#ifndef DEVO_PLAN_BLOCKS
-#define DEVO_PLAN_BLOCKS 1                          // 0: number the bins band by band (A/B builds)
-#endif
-constexpr int CORR_PLAN_BB = DEVO_PLAN_BLOCKS ? 4 : 1;   // bands per block of the plan's bin numbering (4 x 16 rows)
+constexpr int CORR_PLAN_BB = 4;                  // bands per block of the plan's bin numbering (4 x 16 rows)
 __host__ __device__ __forceinline__ int corr_plan_bx(int xw) {   // column bins per block (~64 px)
-  const int b = DEVO_PLAN_BLOCKS ? 64 / (xw > 0 ? xw : 64) : 1;
+  const int b = 64 / (xw > 0 ? xw : 64);
   return b < 1 ? 1 : b;
 }
 
@@ -99,7 +94,7 @@ __device__ __forceinline__ int corr_plan_bin(const int* x, const int* y, float c
   // edge of BASELINE's stress configuration was HEAVY, i.e. unsorted, and its lookup ran at half speed) — which includes every
   // box the staged kernel's tile cannot hold: the long items start first
   if ((long long)(xhi - xlo + D) * (yhi - ylo + D) > (ng == 1 ? 128 : 256) || !tile_fits(xhi - xlo + D, yhi - ylo + D, ng)) return -1;
-  int band = (int)(fminf(fmaxf(centre_y, 0.0f), (float)(H2 - 1))) / DEVO_PLAN_BAND;
+  int band = (int)(fminf(fmaxf(centre_y, 0.0f), (float)(H2 - 1))) / CORR_PLAN_BAND;
   band = min(max(band, 0), nb - 1);
   int xb = (int)(fminf(fmaxf(centre_x, 0.0f), 1.0e6f)) / xw;
   xb = min(max(xb, 0), nxb - 1);
@@ -129,7 +124,7 @@ inline long long corr_plan_bins_per_frame(const CorrPlanGeom& g) {
   return (long long)nbb * nbx * CORR_PLAN_BB * bx;         // (whole blocks: a little more than nb * nxb)
 }
 inline CorrPlanGeom corr_plan_geom(long long B, int n2, int H2) {
-  CorrPlanGeom g{(H2 + DEVO_PLAN_BAND - 1) / DEVO_PLAN_BAND, 1, 8};
+  CorrPlanGeom g{(H2 + CORR_PLAN_BAND - 1) / CORR_PLAN_BAND, 1, 8};
   while (B * n2 * ((g.nb + CORR_PLAN_BB - 1) / CORR_PLAN_BB * CORR_PLAN_BB) > CORR_ORDER_MAXBINS && g.nb > 1) g.nb = (g.nb + 1) / 2;
   if (B * n2 * ((g.nb + CORR_PLAN_BB - 1) / CORR_PLAN_BB * CORR_PLAN_BB) > CORR_ORDER_MAXBINS || g.nb > 255) { g.nb = 0; return g; }
   const int want = (2 * H2 + 7) / 8;                      // 8-px columns across a 2:1 frame

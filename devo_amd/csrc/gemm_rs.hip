@@ -17,8 +17,6 @@
 #include "common.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
-#include <cstdlib>
-#include <vector>
 
 namespace devo {
 
@@ -58,9 +56,7 @@ __global__ __launch_bounds__(256) void k_rs_pack_f16(const __half* __restrict__ 
 template <int MT, int NK>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4 : 1, MT <= 3 ? 4 : 8))) void k_rs_linear_f16(const __half* __restrict__ x, int64_t ldx, const rs_u4* __restrict__ wimg,
                                                         const __half* __restrict__ bias, const __half* residual, __half* y, int64_t ldy, int M,
-                                                        int NB, int K, int relu_from, unsigned long long* trace) {
-  unsigned long long tst[6] = {0, 0, 0, 0, 0, 0};                      // DEVO_RS_TRACE: cycle stamps of every workgroup's wave 0
-  tst[0] = __builtin_readcyclecounter();
+                                                        int NB, int K, int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char rs_lds[];
   constexpr int KP = 32 * NK, PITCH = 2 * KP + 16, PPR = KP / 8, ROWS = 16 * MT;
   constexpr int NPIECE = ROWS * PPR, AP = (NPIECE + 511) / 512;
@@ -98,9 +94,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
     }
     if (p < NPIECE) *reinterpret_cast<rs_u4*>(rs_lds + row * PITCH + 16 * c) = ap[i];
   }
-  tst[1] = __builtin_readcyclecounter();
   __syncthreads();
-  tst[2] = __builtin_readcyclecounter();
   const unsigned char* arow = rs_lds + mi * PITCH + 16 * kg;          // this lane's piece of row 16 mt + mi, K step s: + 16 mt PITCH + 64 s
   float* tile = reinterpret_cast<float*>(rs_lds) + wv * (16 * RS_EPI_LD);
   for (int nb = 0; nb < NB; nb++) {
@@ -127,7 +121,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
           acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, b[s % RS_RB][t]), __builtin_bit_cast(rs_h8, af[s & 1][mt]), acc[mt][t], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
-    tst[3] = __builtin_readcyclecounter();
     // the next pass's first weights travel while this one's results leave
     if (nb + 1 < NB) {
 #pragma unroll
@@ -175,14 +168,6 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();                                 // the tile is read before the next row tile overwrites it
     }
-  }
-  if (trace && tid == 0) {
-    tst[4] = __builtin_readcyclecounter();
-    unsigned hw;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    tst[5] = hw;
-#pragma unroll
-    for (int i = 0; i < 6; i++) trace[6 * blockIdx.x + i] = tst[i];
   }
 }
 
@@ -253,7 +238,6 @@ struct RsGru {
   __half* net_out; __half* delta; __half* weight;
   float* net_out32;                                                    // OUT32 instantiation: the new state in fp32 (what autocast returns)
   int E; float eps0, eps2;
-  unsigned long long* trace;                                           // debug (DEVO_RS_TRACE): 24 cycle stamps of every workgroup's wave 0
 };
 
 constexpr int RG_MT = 6, RG_NK = 12, RG_PITCH = 2 * 32 * RG_NK + 16, RG_ROWS = 16 * RG_MT;
@@ -264,10 +248,6 @@ static_assert(RG_LDS <= 160 * 1024, "the chain's LDS");
 template <bool OUT32>
 __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char rs_lds[];
-  unsigned long long tst[24];
-  int nst = 0;
-  auto stamp = [&]() { if (a.trace) { if (nst < 24) tst[nst] = __builtin_readcyclecounter(); nst++; } };
-  stamp();
   constexpr int MT = RG_MT, NK = RG_NK, PITCH = RG_PITCH, ROWS = RG_ROWS, D = 384;
   unsigned char* X = rs_lds;
   unsigned char* R = rs_lds + ROWS * PITCH;
@@ -346,9 +326,7 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       }
     }
   }
-  stamp();
   __syncthreads();
-  stamp();
   const unsigned char* arowX = X + mi * PITCH + 16 * kg;
   const unsigned char* arowR = R + mi * PITCH + 16 * kg;
   // the weights are the A operand of the products: this lane holds row 16 mt + mi, columns colw + 16 t .. + 3 of a result
@@ -366,7 +344,6 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
     rs_kloop<MT, NK, PITCH, true>(arowX, rs_gr[rep], wbase(1), bvoff, b, acc, rs_r2[rep], wbase(0));
-    stamp();
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
       const rs_f4 bs = vec4(o_gr + D, t);
@@ -378,18 +355,14 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
         *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
       }
     }
-    stamp();
     __syncthreads();
-    stamp();
     // ---- res = R Wr2 + br2 -> this lane's own elements of R (once every wave has read R)
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
     rs_kloop<MT, NK, PITCH, true>(arowR, rs_r2[rep], wbase(0), bvoff, b, acc, rs_gr[rep], wbase(0));
-    stamp();
     __syncthreads();
-    stamp();
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
       const rs_f4 bs = vec4(o_r2, t);
@@ -401,10 +374,8 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
-    stamp();
     if (rep == 0) rs_kloop<MT, NK, PITCH, true>(arowX, rs_gr[0], wbase(0), bvoff, b, acc, rs_gr[1], wbase(1));
     else rs_kloop<MT, NK, PITCH>(arowX, rs_gr[1], wbase(0), bvoff, b, acc);
-    stamp();
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
       const rs_f4 bs = vec4(o_gr, t);
@@ -417,7 +388,6 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
         for (int r = 0; r < 4; r++) acc[mt][t][r] = xv[r] + res[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-gv[r]));
       }
     }
-    stamp();
     if (rep == 0) {
       // ---- X = LN2(t): a row's sums over this wave's 48 columns (12 in this lane, then over the four lanes of the row), then over the
       //      eight waves through LDS
@@ -459,7 +429,6 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       __syncthreads();
     }
   }
-  stamp();
   // ---- net out (whole rows) and the two heads on relu(net): a quarter wave per row
   {
     const int l16 = tid & 15;
@@ -507,11 +476,6 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
         a.weight[(int64_t)row * 2 + 1] = __float2half(1.0f / (1.0f + __expf(-(w1 + bw1))));
       }
     }
-  }
-  stamp();
-  if (a.trace && tid == 0) {
-#pragma unroll
-    for (int i = 0; i < 24; i++) a.trace[24 * blockIdx.x + i] = i < nst ? tst[i] : 0ull;
   }
 }
 
@@ -1115,7 +1079,7 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
 
 template <int MT, int NK>
 static int rs_launch(const void* x, int64_t ldx, const void* wimg, const void* bias, const void* residual, void* y, int64_t ldy, int M, int NB, int K,
-                     int relu_from, hipStream_t stream, unsigned long long* trace = nullptr) {
+                     int relu_from, hipStream_t stream) {
   constexpr int ROWS = 16 * MT, PITCH = 2 * 32 * NK + 16;
   // the row tile; the last pass's result tiles lie over it (26.6 KB: more than a 32-row tile), earlier passes' behind it
   const int lds = std::max(ROWS * PITCH, RS_NW * 16 * RS_EPI_LD * 4) + (NB > 1 ? RS_NW * 16 * RS_EPI_LD * 4 : 0);
@@ -1125,7 +1089,7 @@ static int rs_launch(const void* x, int64_t ldx, const void* wimg, const void* b
                  "devo_upd_rs_linear_f16: cannot raise the dynamic LDS limit");
   }
   hipLaunchKernelGGL((k_rs_linear_f16<MT, NK>), dim3((unsigned)((M + ROWS - 1) / ROWS)), dim3(512), lds, stream, (const __half*)x, ldx, (const rs_u4*)wimg,
-                     (const __half*)bias, (const __half*)residual, (__half*)y, ldy, M, NB, K, relu_from, trace);
+                     (const __half*)bias, (const __half*)residual, (__half*)y, ldy, M, NB, K, relu_from);
   return check_launch("devo_upd_rs_linear_f16");
 }
 
@@ -1175,43 +1139,13 @@ int devo_upd_rs_linear_f16(const void* x, int64_t ldx, const void* wimg, const v
   DEVO_REQUIRE(!(ldy & 7) && !(reinterpret_cast<uintptr_t>(y) & 15) && !(reinterpret_cast<uintptr_t>(residual) & 15) && !(ldx & 1) && !(reinterpret_cast<uintptr_t>(x) & 3),
                "devo_upd_rs_linear_f16: alignment (y / residual rows 16 bytes, x rows 4 bytes)");
   DEVO_REQUIRE(((int64_t)(M - 1) * ldx + K) * 2 < (1ll << 31), "devo_upd_rs_linear_f16: x beyond 2 GB");
-  static const int mt = [] { const char* e = getenv("DEVO_RS_MT"); return e ? atoi(e) : 6; }();
   const int NB = N / RS_BN;
   if (relu_from < 0) relu_from = 0;
-  static const bool tr = getenv("DEVO_RS_TRACE") != nullptr;          // debug: stamps of one launch (synchronous), summary on stderr
-  if (tr) {
-    const int rows = mt == 6 ? 96 : mt == 4 ? 64 : mt == 3 ? 48 : mt == 2 ? 32 : 128, nwg = (M + rows - 1) / rows;
-    unsigned long long* d = nullptr;
-    if (hipMalloc(&d, (size_t)nwg * 48) != hipSuccess) return DEVO_ERR_LAUNCH;
-    int rc = mt == 6 ? rs_launch<6, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream, d)
-           : mt == 4 ? rs_launch<4, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream, d)
-           : mt == 3 ? rs_launch<3, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream, d)
-           : mt == 2 ? rs_launch<2, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream, d)
-                     : rs_launch<8, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream, d);
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    std::vector<unsigned long long> h((size_t)nwg * 6);
-    (void)hipMemcpy(h.data(), d, h.size() * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(d);
-    double ph[4] = {0, 0, 0, 0};
-    unsigned long long lo = ~0ull, hi = 0;
-    for (int g = 0; g < nwg; g++) {
-      for (int i = 0; i < 4; i++) ph[i] += (double)(h[6 * g + i + 1] - h[6 * g + i]);
-      lo = std::min(lo, h[6 * g]); hi = std::max(hi, h[6 * g + 4]);
-    }
-    fprintf(stderr, "rs trace: %d workgroups x %d rows, NB %d: mean cycles rows->LDS %.0f | barrier %.0f | K loops (all but the last pass's epilogue) %.0f | last epilogue %.0f | first start to last end %llu\n",
-            nwg, rows, NB, ph[0] / nwg, ph[1] / nwg, ph[2] / nwg, ph[3] / nwg, hi - lo);
-    return rc;
-  }
   // few rows (the SoftAggs' h layers: 1 440 / 210 rows at cfg2, 2 112 at the steady-state graph): 32-row workgroups — the products of a 96-row tile
   // on three CUs are time added to the latency of the weight stream, which is what such a launch consists of (9.4 -> ~6 us).  Swept in round 6
-  // (tools/exp_r06y.sh): 32 rows win up to 12 288 rows (2 112: 9.1 -> 5.3 us, 8 192: 9.9 -> 7.4, 12 288: 10.6 -> 10.0), 96 rows at 21 600 (12.8 / 15.0)
-  static const int small_m = [] { const char* e = getenv("DEVO_RS_SMALL_M"); return e ? atoi(e) : 12288; }();   // (tuning switch)
-  if (M <= small_m && !getenv("DEVO_RS_MT")) return rs_launch<2, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
-  if (mt == 6) return rs_launch<6, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
-  if (mt == 2) return rs_launch<2, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
-  if (mt == 3) return rs_launch<3, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
-  if (mt == 4) return rs_launch<4, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
-  return rs_launch<8, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
+  // (profiles/r06_rs_small_m.txt): 32 rows win up to 12 288 rows (2 112: 9.1 -> 5.3 us, 8 192: 9.9 -> 7.4, 12 288: 10.6 -> 10.0), 96 rows at 21 600 (12.8 / 15.0)
+  if (M <= 12288) return rs_launch<2, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
+  return rs_launch<6, 12>(x, ldx, wimg, bias, residual, y, ldy, M, NB, K, relu_from, (hipStream_t)stream);
 }
 
 
@@ -1242,27 +1176,10 @@ static int rs_gru_impl(const void* x, const void* hy, const int* group_of, const
   a.w_gr[1] = (const rs_u4*)wgr3_img; a.b_gr[1] = (const __half*)bgr3; a.w_r2[1] = (const rs_u4*)wr2_3_img; a.b_r2[1] = (const __half*)br2_3;
   a.ln2_g = (const __half*)ln2_w; a.ln2_b = (const __half*)ln2_b; a.Wd = (const __half*)Wd; a.bd = (const __half*)bd; a.Ww = (const __half*)Ww; a.bw = (const __half*)bw;
   a.net_out = out32 ? nullptr : (__half*)net_out; a.net_out32 = out32 ? (float*)net_out : nullptr;
-  a.delta = (__half*)delta; a.weight = (__half*)weight; a.E = E; a.eps0 = eps0; a.eps2 = eps2; a.trace = nullptr;
+  a.delta = (__half*)delta; a.weight = (__half*)weight; a.E = E; a.eps0 = eps0; a.eps2 = eps2;
   const int nwg = (E + RG_ROWS - 1) / RG_ROWS;
-  static const bool tr = getenv("DEVO_RS_TRACE") != nullptr;          // debug: stamps of this launch (synchronous), mean cycles per phase on stderr
-  if (tr && hipMalloc(&a.trace, (size_t)nwg * 24 * 8) != hipSuccess) a.trace = nullptr;
   if (out32) hipLaunchKernelGGL(k_rs_gru_f16<true>, dim3((unsigned)nwg), dim3(512), RG_LDS, (hipStream_t)stream, a);
   else hipLaunchKernelGGL(k_rs_gru_f16<false>, dim3((unsigned)nwg), dim3(512), RG_LDS, (hipStream_t)stream, a);
-  if (a.trace) {
-    (void)hipStreamSynchronize((hipStream_t)stream);
-    std::vector<unsigned long long> h((size_t)nwg * 24);
-    (void)hipMemcpy(h.data(), a.trace, h.size() * 8, hipMemcpyDeviceToHost);
-    (void)hipFree(a.trace);
-    fprintf(stderr, "rs gru trace (%d workgroups), mean cycles per phase:", nwg);
-    for (int i = 0; i + 1 < 24; i++) {
-      double d = 0; int n = 0;
-      for (int g = 0; g < nwg; g++) if (h[24 * g + i + 1]) { d += (double)(h[24 * g + i + 1] - h[24 * g + i]); n++; }
-      if (n) fprintf(stderr, " %.0f", d / n);
-    }
-    double tot = 0;
-    for (int g = 0; g < nwg; g++) { int l = 23; while (l > 0 && !h[24 * g + l]) l--; tot += (double)(h[24 * g + l] - h[24 * g]); }
-    fprintf(stderr, " | total %.0f\n", tot / nwg);
-  }
   return check_launch("devo_upd_rs_gru_f16");
 }
 int devo_upd_rs_gru_f16(const void* x, const void* hy, const int* group_of, const void* ln0_w, const void* ln0_b, float eps0, const void* wgr1_img,

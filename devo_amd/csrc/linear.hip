@@ -27,8 +27,6 @@
 #include "common.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
-#include <map>
-#include <vector>
 
 namespace devo {
 
@@ -121,18 +119,12 @@ __device__ __forceinline__ void ln_dma16(unsigned voff, __amdgpu_buffer_rsrc_t r
 
 // y[M, N] = act(x[M, K] B + bias), B = the split weight image.  grid = 8 * ceil(row blocks / 8) * (N / 96), one row block's column
 // blocks on one XCD.
-template <bool TRACE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_linear_split(
     const float* __restrict__ x, int64_t ldx, const ln_u4* __restrict__ wsplit, const float* __restrict__ bias, const float* residual,
-    const float* __restrict__ gate, float* y, int64_t ldy, int M, int N, int K, int relu_from, int dbg, unsigned long long* wgtrace) {
+    const float* __restrict__ gate, float* y, int64_t ldy, int M, int N, int K, int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char ln_lds[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int NB = (N + LN_BN - 1) / LN_BN, Np = NB * LN_BN, nk = (K + 31) / 32;
-  // DEVO_LN_DBG: 1 no activation loads, 2 no stores, 4 no weight DMA, 8 no MFMAs, 16 cycle stamps of workgroup 0 into y[0][..]
-  unsigned long long tst[32];
-  int nst = 0;
-  auto stamp = [&]() { if constexpr (TRACE) { if (nst < 32) tst[nst] = __builtin_readcyclecounter(); nst++; } };
-  stamp();
   const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3;
   const int rb = (slot / NB) * 8 + xcd, nb = slot - (slot / NB) * NB;
   if (rb * LN_BM >= M) return;
@@ -148,7 +140,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
   for (int q = 0; q < 4; q++) {
     const int row = row_w + 8 * q + (lane >> 3);
-    avoff[q] = (row < M && !(dbg & 1)) ? (unsigned)(((int64_t)row * ldx) * 4 + 16 * ((lane & 7) ^ ((lane >> 3) & 7))) : OFF_NONE;
+    avoff[q] = row < M ? (unsigned)(((int64_t)row * ldx) * 4 + 16 * ((lane & 7) ^ ((lane >> 3) & 7))) : OFF_NONE;
   }
   unsigned aslot[LN_MT][2];                                           // byte offsets of this lane's two pieces (channels 8 kg .. + 7) of row 16 mt + mi
 #pragma unroll
@@ -168,7 +160,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   // carry the out-of-range offset: no memory access, zeros back
   auto stage = [&](int s) {                                          // this wave's 3 of the stage's 12 one-KB pieces
     const int buf = s % LN_NSTAGE;
-    const unsigned voff = (s < nk && !(dbg & 4)) ? (unsigned)lane * 16u : OFF_NONE;
+    const unsigned voff = s < nk ? (unsigned)lane * 16u : OFF_NONE;
 #pragma unroll
     for (int q = 0; q < LN_NT * 2 / 4; q++) {
       const int piece = wv + 4 * q;
@@ -195,7 +187,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   stage(1);
   asm volatile("s_waitcnt vmcnt(3)" ::: "memory");                    // (the second stage's three requests may stay in flight)
   __syncthreads();
-  stamp();
 
   auto step = [&](int s) {
     // this step's activations out of the slab, then the slab is free for the next step's (requested one step ahead; the weight pieces two)
@@ -207,7 +198,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     load_a(s + 1);
     stage(s + 2);
-    stamp();
     // ---- scale: this lane's 2 x 8 values against the row scales
     float xv[LN_MT][8];
     float mx[LN_MT];
@@ -259,8 +249,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       ln_split8(xv[mt], ah[mt], al[mt]);
     }
     const ln_u4* sb = reinterpret_cast<const ln_u4*>(ln_lds + (s % LN_NSTAGE) * LN_STAGE) + lane;
-    stamp();
-    if (!(dbg & 8))
+    __builtin_amdgcn_sched_barrier(0);                                 // the products start behind the split (interleaved: 8 more VGPRs)
 #pragma unroll
     for (int tg = 0; tg < LN_NT; tg += 3) {
       ln_h8 bh[3], bl[3];
@@ -283,11 +272,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         for (int mt = 0; mt < LN_MT; mt++) acc[mt][tg + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(ah[mt], bh[u], acc[mt][tg + u], 0, 0, 0);
     }
     // step s + 1's activations (requested in this step) and weight pieces (one step ago) have landed; this step's 3 weight requests may stay in flight
-    stamp();
     asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
-    stamp();
     __syncthreads();                                                   // every wave is done with this stage's buffer
-    stamp();
   };
   for (int s = 0; s < nk; s++) step(s);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                    // the trailing (empty) requests, before the ring becomes the result tile
@@ -316,7 +302,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       v = v * rowf[16 * mt + r] * *reinterpret_cast<const ln_f4*>(colf + 4 * c4) + *reinterpret_cast<const ln_f4*>(colf + LN_BN + 4 * c4);
       if (col0 + 4 * c4 >= relu_from) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
       const int row = row_w + 16 * mt + r, col = col0 + 4 * c4;
-      if (row < M && col < N && !(dbg & 2)) {
+      if (row < M && col < N) {
         float* dst = y + (int64_t)row * ldy + col;
         const float* res = residual ? residual + (int64_t)row * ldy + col : nullptr;      // (may be y itself: read, then written, by this lane)
         const float* gt = gate ? gate + (int64_t)row * ldy + col : nullptr;      // a ReLU's output: this gradient passes where it did not clip
@@ -336,19 +322,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     }
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
     __builtin_amdgcn_wave_barrier();                                   // the tile is read before the next row tile overwrites it
-  }
-  stamp();
-  if (TRACE && wgtrace && tid == 0) {                                  // DEVO_LN_DBG = 48: every workgroup's start / end / hardware id
-    unsigned hw, xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-    wgtrace[4 * blockIdx.x + 0] = tst[0]; wgtrace[4 * blockIdx.x + 1] = __builtin_readcyclecounter();
-    wgtrace[4 * blockIdx.x + 2] = hw; wgtrace[4 * blockIdx.x + 3] = xcc;
-  }
-  if (TRACE && !wgtrace && blockIdx.x == 0 && tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int i = 0; i < 32; i++) y[i] = i < nst ? (float)(long long)(tst[i] - tst[0]) : -1.f;
   }
 }
 
@@ -539,37 +512,8 @@ int devo_upd_linear_split(const float* x, int64_t ldx, const void* wsplit, const
   DEVO_REQUIRE(((int64_t)(M - 1) * ldx + K) * 4 < (1LL << 31) && (int64_t)NB * LN_BN * nk * 128 < (1LL << 31), "devo_upd_linear_split: operand beyond 2 GB");
   static_assert(LN_LDS <= 64 * 1024, "the workgroup's LDS fits the default dynamic limit");
   const int RB = (M + LN_BM - 1) / LN_BM;
-  static const int dbg = getenv("DEVO_LN_DBG") ? atoi(getenv("DEVO_LN_DBG")) : 0;
-  const unsigned nwg = (unsigned)(((RB + 7) / 8) * 8 * NB);
-  unsigned long long* wgtrace = nullptr;
-  if ((dbg & 48) == 48) { (void)hipMalloc(&wgtrace, (size_t)nwg * 32); (void)hipMemset(wgtrace, 0, (size_t)nwg * 32); }
-  hipLaunchKernelGGL((dbg & 16) ? k_linear_split<true> : k_linear_split<false>, dim3(nwg), dim3(256), LN_LDS, (hipStream_t)stream, x, ldx,
-                     (const ln_u4*)wsplit, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from, dbg, wgtrace);
-  if (wgtrace) {                                                      // debug: residency of the launch's workgroups over time, per CU
-    (void)hipDeviceSynchronize();
-    std::vector<unsigned long long> h((size_t)nwg * 4);
-    (void)hipMemcpy(h.data(), wgtrace, (size_t)nwg * 32, hipMemcpyDeviceToHost);
-    (void)hipFree(wgtrace);
-    unsigned long long t0 = ~0ull, t1 = 0;
-    double sum = 0; int cnt = 0;
-    std::map<unsigned long long, std::vector<std::pair<unsigned long long, unsigned long long>>> per_cu;
-    for (unsigned i = 0; i < nwg; i++) {
-      if (!h[4 * i + 1]) continue;
-      t0 = std::min(t0, h[4 * i]); t1 = std::max(t1, h[4 * i + 1]); sum += (double)(h[4 * i + 1] - h[4 * i]); cnt++;
-      per_cu[((h[4 * i + 3] & 15) << 16) | (h[4 * i + 2] & 0xff00)].push_back({h[4 * i], h[4 * i + 1]});      // XCC | SE, SH, CU
-    }
-    int maxc = 0; double avgc = 0;
-    for (auto& kv : per_cu) {
-      int best = 0;
-      for (auto& a : kv.second) { int c = 0; for (auto& b : kv.second) c += (b.first <= a.first && a.first < b.second); best = std::max(best, c); }
-      maxc = std::max(maxc, best); avgc += best;
-    }
-    fprintf(stderr, "[linear trace] %d workgroups on %zu CUs, span %llu cycles, mean workgroup %0.f cycles; most workgroups resident on one CU at a time: max %d, mean over CUs %.2f\n",
-            cnt, per_cu.size(), t1 - t0, sum / std::max(cnt, 1), maxc, avgc / std::max<size_t>(per_cu.size(), 1));
-    unsigned long long last_start = 0;
-    for (unsigned i = 0; i < nwg; i++) if (h[4 * i + 1]) last_start = std::max(last_start, h[4 * i] - t0);
-    fprintf(stderr, "[linear trace] the last workgroup starts %llu cycles after the first\n", last_start);
-  }
+  hipLaunchKernelGGL(k_linear_split, dim3((unsigned)(((RB + 7) / 8) * 8 * NB)), dim3(256), LN_LDS, (hipStream_t)stream, x, ldx,
+                     (const ln_u4*)wsplit, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
   return check_launch("devo_upd_linear_split");
 }
 

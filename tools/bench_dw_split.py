@@ -29,5 +29,5 @@ for rows, no, ni in [(18000, 384, 384), (18000, 768, 384), (18000, 384, 768)]:
     t_own = timed(lambda: U._dw_split(dy, x, True))
     ref = dy.double().t() @ x.double()
     e_lib = (lib()[0].double() - ref).abs().max().item(); e_own = (U._dw_split(dy, x, True)[0].double() - ref).abs().max().item()
-    print(f"{rows} rows, {no} x {ni}: library (16 row chunks + sum + bias sum) {t_lib:.1f} us, library direct {t_direct:.1f} us, split {t_own:.1f} us "
-          f"(DEVO_DW_SPLITS={os.environ.get('DEVO_DW_SPLITS', 'auto')}); max |err| vs float64: library {e_lib:.2e}, split {e_own:.2e}")
+    print(f"{rows} rows, {no} x {ni}: library (16 row chunks + sum + bias sum) {t_lib:.1f} us, library direct {t_direct:.1f} us, split {t_own:.1f} us; "
+          f"max |err| vs float64: library {e_lib:.2e}, split {e_own:.2e}")

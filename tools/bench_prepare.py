@@ -29,11 +29,3 @@ for name, (kk, Np, N) in cases.items():
     ref = torch.unique(kk)
     assert n == ref.numel() and torch.equal(kx.long(), ref)
     print(f"{name}: {ev0.elapsed_time(ev1) / 50 * 1e3:.1f} us per prepare")
-    import ctypes
-    from devo_amd import _lib as L
-    if hasattr(L.lib(), "devo_debug_prep_trace"):
-        buf = (ctypes.c_ulonglong * 16)()
-        L.lib().devo_debug_prep_trace(buf)
-        st = [buf[i] for i in range(9)]
-        names = ["kk loaded + ascending test", "range + flags", "ids ranked (scan)", "segments counted", "segment starts (scan)", "scattered", "starts published", "segments sorted"]
-        print("   phases (us): " + ", ".join(f"{n} {(st[i + 1] - st[i]) / 100.0:.1f}" for i, n in enumerate(names) if st[i + 1] > st[i]))

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """csrc/gemm_rs.hip (rows in LDS once, weights from the L2 into registers) against csrc/linear.hip's k_linear_f16: identical results,
-HIP-graph replays, us per layer at the update operator's shapes.  DEVO_RS_MT = 4 / 6 / 8 row tiles per workgroup."""
+HIP-graph replays, us per layer at the update operator's shapes (32-row workgroups up to 12 288 rows, else 96)."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
