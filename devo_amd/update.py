@@ -19,6 +19,24 @@ from .backends import cuda_ba
 DIM = 384
 
 
+def _switch(name):
+    """A module switch from the environment: on unless the variable is "0" (tests and tools also set the attributes below directly)"""
+    return os.environ.get(name, "1") != "0"
+
+
+SPLIT_GEMM = _switch("DEVO_UPD_SPLIT_GEMM")          # 0: the library's fp32 GEMMs for every Linear layer
+F16_GEMM = _switch("DEVO_UPD_F16_GEMM")              # 0: the library's GEMMs for the fp16 operator
+RS_GEMM = _switch("DEVO_UPD_RS")                     # 0: every fp16 Linear layer on csrc/linear.hip's kernel
+RS_CHAINS = _switch("DEVO_UPD_RS_CHAINS")            # 0: no row-resident chains (one launch per layer / LayerNorm)
+MLP2_F16 = _switch("DEVO_UPD_MLP2")                  # 0: Linear - ReLU - Linear chains as two launches
+MIXED_STATE = _switch("DEVO_UPD_MIXED_STATE")        # 0: the autocast call converts the fp32 state with torch in front of / behind the fp16 operator
+AUTOCAST_F16 = _switch("DEVO_UPD_AUTOCAST_F16")      # 0: an fp32 operator called under autocast keeps its fp32 kernels
+RS_SPLIT = _switch("DEVO_UPD_RS_SPLIT")              # 0: every fp32 Linear layer on csrc/linear.hip's kernel
+SPLIT_DW = _switch("DEVO_UPD_SPLIT_DW")              # 0: the library's products for dW / db
+FUSE_EPILOGUE = _switch("DEVO_UPD_FUSE_EPILOGUE")    # 0: ReLU / residual sums as ATen kernels in the training path
+HIP_LAYERNORM = _switch("DEVO_UPD_HIP_LAYERNORM")    # 0: ATen's LayerNorm in the training path
+
+
 class _GradClip(torch.autograd.Function):            # blocks.py:72-81: identity forward; backward NaN -> 0, clamp +-0.01
     @staticmethod
     def forward(ctx, x):
@@ -29,40 +47,49 @@ class _GradClip(torch.autograd.Function):            # blocks.py:72-81: identity
         return torch.nan_to_num(grad, nan=0.0, posinf=float("inf"), neginf=float("-inf")).clamp(min=-0.01, max=0.01)
 
 
-
-_wsplit_cache = {}          # (ptr, version, shape, strides, transposed) -> (weight [kept alive], its split image); LRU
+_wsplit_cache = {}          # (ptr, version, shape, strides, kind) -> (weight [kept alive], its operand image of that kind); LRU
 WSPLIT_CACHE_ENTRIES = 96
-SPLIT_GEMM = __import__("os").environ.get("DEVO_UPD_SPLIT_GEMM", "1") != "0"     # 0: the library's fp32 GEMMs for every Linear layer
+
+
+def _weight_image(w, kind, build):
+    """build(w) — a weight's packed operand image of one kind — cached per VERSION of the weight: a training step's 18 update iterations
+    split each layer twice (forward, dX), not 36 times; the optimiser's in-place step bumps the version.  A hit moves to the young end;
+    a miss drops the older versions of this weight's image of this kind, then the oldest entries down to WSPLIT_CACHE_ENTRIES.  (The cache
+    holds the weight, so its storage cannot be handed to another tensor; an edit through `.data`, which has its own version counter, is
+    NOT seen — like Update._cat's concatenated weights: assign parameters with copy_ / load_state_dict / optimiser steps.)"""
+    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), kind)
+    hit = _wsplit_cache.pop(key, None)
+    if hit is None:
+        for k in [k for k in _wsplit_cache if k[0] == key[0] and k[4] == kind]:
+            del _wsplit_cache[k]
+        while len(_wsplit_cache) >= WSPLIT_CACHE_ENTRIES:
+            del _wsplit_cache[next(iter(_wsplit_cache))]
+        hit = (w, build(w))
+    _wsplit_cache[key] = hit
+    return hit[1]
+
+
+def _b_operand(w, transposed):
+    """(N, K, stride along N, stride along K) of a Linear weight as the B operand of `x @ w.T` (transposed=False) or `g @ w` (True)"""
+    (out_f, in_f), (s_o, s_i) = w.shape, w.stride()
+    return (in_f, out_f, s_i, s_o) if transposed else (out_f, in_f, s_o, s_i)
 
 
 def _split_weight(w, transposed):
     """The B-operand image of csrc/linear.hip for `x @ w.T` (transposed=False) or `g @ w` (True): every fp32 weight as an exact fp16
-    hi + lo pair, one 1 KB piece per (K step, column tile).  Cached per version of the weight: a training step's 18 update iterations
-    split each layer twice (forward, dX), not 36 times; the optimiser's in-place step bumps the version.  (The cache holds the weight, so its
-    storage cannot be handed to another tensor; an edit through `.data`, which has its own version counter, is NOT seen — like Update._cat's
-    concatenated weights: assign parameters with copy_ / load_state_dict / optimiser steps.)"""
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), transposed)
-    hit = _wsplit_cache.pop(key, None)
-    if hit is not None:
-        _wsplit_cache[key] = hit
-        return hit[1]
-    for k in [k for k in _wsplit_cache if k[0] == key[0] and k[4] == transposed]:
-        del _wsplit_cache[k]
-    while len(_wsplit_cache) >= WSPLIT_CACHE_ENTRIES:
-        del _wsplit_cache[next(iter(_wsplit_cache))]
-    out_f, in_f = w.shape
-    N, K = (in_f, out_f) if transposed else (out_f, in_f)
-    s_n, s_k = (w.stride(1), w.stride(0)) if transposed else (w.stride(0), w.stride(1))
-    if w.dtype == torch.float16:                                       # fp16 storage: the operand image only (no split, no scales)
-        img = torch.empty(N * ((K + 63) // 64 * 64), dtype=torch.float16, device=w.device)
-        L.check(L.lib().devo_upd_pack_weight_f16(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.pack_weight_f16")
-    else:
-        Np = (N + 95) // 96 * 96                                        # (whole column blocks of 96: zero columns behind N)
-        img = torch.empty(int(L.lib().devo_upd_split_weight_bytes(N, K)) // 4, dtype=torch.float32, device=w.device)
-        assert img.numel() == Np * ((K + 31) // 32 * 32) + Np
-        L.check(L.lib().devo_upd_split_weight(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.split_weight")
-    _wsplit_cache[key] = (w, img)
-    return img
+    hi + lo pair, one 1 KB piece per (K step, column tile); cached (_weight_image)."""
+    def build(w):
+        N, K, s_n, s_k = _b_operand(w, transposed)
+        if w.dtype == torch.float16:                                       # fp16 storage: the operand image only (no split, no scales)
+            img = torch.empty(N * ((K + 63) // 64 * 64), dtype=torch.float16, device=w.device)
+            L.check(L.lib().devo_upd_pack_weight_f16(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.pack_weight_f16")
+        else:
+            Np = (N + 95) // 96 * 96                                        # (whole column blocks of 96: zero columns behind N)
+            img = torch.empty(int(L.lib().devo_upd_split_weight_bytes(N, K)) // 4, dtype=torch.float32, device=w.device)
+            assert img.numel() == Np * ((K + 31) // 32 * 32) + Np
+            L.check(L.lib().devo_upd_split_weight(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.split_weight")
+        return img
+    return _weight_image(w, transposed, build)
 
 
 def invalidate_weight_images():
@@ -78,35 +105,22 @@ def _split_ok(x2, n_out, k_in):
             ((x2.shape[0] - 1) * x2.stride(0) + k_in) * 4 < (1 << 31))
 
 
-F16_GEMM = __import__("os").environ.get("DEVO_UPD_F16_GEMM", "1") != "0"          # 0: the library's GEMMs for the fp16 operator
-
-
 def _f16_ok(x2, n_out, k_in):
     return (F16_GEMM and x2.is_cuda and x2.dtype == torch.float16 and x2.dim() == 2 and x2.stride(1) == 1 and x2.stride(0) >= k_in
             and x2.stride(0) % 2 == 0 and x2.data_ptr() % 4 == 0 and n_out % 96 == 0 and x2.shape[0] >= 1024
             and ((x2.shape[0] - 1) * x2.stride(0) + k_in) * 2 < (1 << 31))
 
 
-RS_GEMM = __import__("os").environ.get("DEVO_UPD_RS", "1") != "0"                # 0: every fp16 Linear layer on csrc/linear.hip's kernel
-RS_CHAINS = __import__("os").environ.get("DEVO_UPD_RS_CHAINS", "1") != "0"       # 0: no row-resident chains (one launch per layer / LayerNorm)
-
-
-def _rs_image(w):
-    """The B-operand image of csrc/gemm_rs.hip for a [384 n, K] fp16 weight, cached per version like _split_weight's images."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), "rs")
-    hit = _wsplit_cache.pop(key, None)
-    if hit is not None:
-        _wsplit_cache[key] = hit
-        return hit[1]
-    for k in [k for k in _wsplit_cache if k[0] == key[0] and k[4] == "rs"]:
-        del _wsplit_cache[k]
-    while len(_wsplit_cache) >= WSPLIT_CACHE_ENTRIES:
-        del _wsplit_cache[next(iter(_wsplit_cache))]
+def _pack_rs(w):
     N, K = w.shape
     img = torch.empty(int(L.lib().devo_upd_rs_weight_bytes(N, K)) // 2, dtype=torch.float16, device=w.device)
     L.check(L.lib().devo_upd_rs_pack_weight_f16(L.ptr(w), w.stride(0), w.stride(1), N, K, L.ptr(img), L.stream()), "update.rs_pack_weight")
-    _wsplit_cache[key] = (w, img)
     return img
+
+
+def _rs_image(w):
+    """The B-operand image of csrc/gemm_rs.hip for a [384 n, K] fp16 weight; cached (_weight_image)."""
+    return _weight_image(w, "rs", _pack_rs)
 
 
 def _linear_f16(x2, w, b, relu=False, relu_from=None, residual=None, out=None):
@@ -126,25 +140,16 @@ def _linear_f16(x2, w, b, relu=False, relu_from=None, residual=None, out=None):
     return y
 
 
-MLP2_F16 = __import__("os").environ.get("DEVO_UPD_MLP2", "1") != "0"            # 0: Linear - ReLU - Linear chains as two launches
+def _pack_mlp2(w):
+    K = w.shape[1]
+    img = torch.empty(int(L.lib().devo_upd_mlp2_weight_bytes(K)) // 2, dtype=torch.float16, device=w.device)
+    L.check(L.lib().devo_upd_mlp2_pack_weight(L.ptr(w), w.stride(0), w.stride(1), K, L.ptr(img), L.stream()), "update.mlp2_pack_weight")
+    return img
 
 
 def _mlp2_image(w):
-    """The B-operand image of csrc/mlp2.hip for a [384, K] fp16 weight, cached per version like _split_weight's images."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), "mlp2")
-    hit = _wsplit_cache.pop(key, None)
-    if hit is not None:
-        _wsplit_cache[key] = hit
-        return hit[1]
-    for k in [k for k in _wsplit_cache if k[0] == key[0] and k[4] == "mlp2"]:
-        del _wsplit_cache[k]
-    while len(_wsplit_cache) >= WSPLIT_CACHE_ENTRIES:
-        del _wsplit_cache[next(iter(_wsplit_cache))]
-    N, K = w.shape
-    img = torch.empty(int(L.lib().devo_upd_mlp2_weight_bytes(K)) // 2, dtype=torch.float16, device=w.device)
-    L.check(L.lib().devo_upd_mlp2_pack_weight(L.ptr(w), w.stride(0), w.stride(1), K, L.ptr(img), L.stream()), "update.mlp2_pack_weight")
-    _wsplit_cache[key] = (w, img)
-    return img
+    """The B-operand image of csrc/mlp2.hip for a [384, K] fp16 weight; cached (_weight_image)."""
+    return _weight_image(w, "mlp2", _pack_mlp2)
 
 
 def _mlp2_ok(x2, l1, l2):
@@ -178,29 +183,14 @@ def _mlp2_f16(x2, l1, l2, residual=None, gather=None, fg=None):
     return y
 
 
-MIXED_STATE = __import__("os").environ.get("DEVO_UPD_MIXED_STATE", "1") != "0"      # 0: the autocast call converts the fp32 state with torch in front of / behind the fp16 operator
-AUTOCAST_F16 = __import__("os").environ.get("DEVO_UPD_AUTOCAST_F16", "1") != "0"    # 0: an fp32 operator called under autocast keeps its fp32 kernels
-RS_SPLIT = __import__("os").environ.get("DEVO_UPD_RS_SPLIT", "1") != "0"         # 0: every fp32 Linear layer on csrc/linear.hip's kernel
-
-
 def _rs_split_image(w, transposed):
-    """The split B-operand image of csrc/gemm_rs.hip for `x @ w.T` (transposed=False) or `g @ w` (True), cached per version like _split_weight's."""
-    key = (w.data_ptr(), w._version, tuple(w.shape), tuple(w.stride()), ("rs32", transposed))
-    hit = _wsplit_cache.pop(key, None)
-    if hit is not None:
-        _wsplit_cache[key] = hit
-        return hit[1]
-    for k in [k for k in _wsplit_cache if k[0] == key[0] and k[4] == key[4]]:
-        del _wsplit_cache[k]
-    while len(_wsplit_cache) >= WSPLIT_CACHE_ENTRIES:
-        del _wsplit_cache[next(iter(_wsplit_cache))]
-    out_f, in_f = w.shape
-    N, K = (in_f, out_f) if transposed else (out_f, in_f)
-    s_n, s_k = (w.stride(1), w.stride(0)) if transposed else (w.stride(0), w.stride(1))
-    img = torch.empty(int(L.lib().devo_upd_rs_split_weight_bytes(N, K)) // 4, dtype=torch.float32, device=w.device)
-    L.check(L.lib().devo_upd_rs_split_weight(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.rs_split_weight")
-    _wsplit_cache[key] = (w, img)
-    return img
+    """The split B-operand image of csrc/gemm_rs.hip for `x @ w.T` (transposed=False) or `g @ w` (True); cached (_weight_image)."""
+    def build(w):
+        N, K, s_n, s_k = _b_operand(w, transposed)
+        img = torch.empty(int(L.lib().devo_upd_rs_split_weight_bytes(N, K)) // 4, dtype=torch.float32, device=w.device)
+        L.check(L.lib().devo_upd_rs_split_weight(L.ptr(w), s_n, s_k, N, K, L.ptr(img), L.stream()), "update.rs_split_weight")
+        return img
+    return _weight_image(w, ("rs32", transposed), build)
 
 
 def _linear_split(x2, w, b, transposed=False, relu=False, relu_from=None, residual=None, out=None, gate=None, rs=False):
@@ -229,7 +219,6 @@ def _linear_split(x2, w, b, transposed=False, relu=False, relu_from=None, residu
 
 
 _dw_ws = {}                 # (device, stream) -> workspace of the weight-gradient kernel (grown on demand, reused: ONE stream serialises its users)
-SPLIT_DW = __import__("os").environ.get("DEVO_UPD_SPLIT_DW", "1") != "0"        # 0: the library's products for dW / db
 
 
 def _dw_ok(g2, x2):
@@ -365,9 +354,6 @@ def _mlp2_fused_ok(seq, x2, residual):
     return ok_fwd and ok_dw
 
 
-FUSE_EPILOGUE = __import__("os").environ.get("DEVO_UPD_FUSE_EPILOGUE", "1") != "0"     # 0: ReLU / residual sums as ATen kernels in the training path
-
-
 def _mlp2(seq, x, residual=None):
     """Sequential(Linear, ReLU, Linear)(x) [+ residual] for the autograd path: the ReLU and the residual sum in the GEMMs' epilogues when
     the rows are the operator's (>= 4096 fp32 rows on the GPU), the modules as they are otherwise"""
@@ -445,9 +431,6 @@ class _LayerNormFn(torch.autograd.Function):
         return (dxv if ctx.needs_input_grad[0] else None, dxv if a2 is not None and ctx.needs_input_grad[1] else None,
                 dxv if b2 is not None and ctx.needs_input_grad[2] else None, dwb[0] if ctx.needs_input_grad[3] else None,
                 dwb[1] if ctx.needs_input_grad[4] else None, None, None)
-
-
-HIP_LAYERNORM = __import__("os").environ.get("DEVO_UPD_HIP_LAYERNORM", "1") != "0"      # 0: ATen's LayerNorm in the training path
 
 
 def _ln_train(mod, x, a=None, b=None, relu=False):
@@ -633,9 +616,6 @@ def _pinned_word():
     return P["pool"][P["next"]]
 
 
-_GRAPH_TABLES = os.environ.get("DEVO_UPD_GRAPH_TABLES", "1") != "0"     # (0: the separate calls of rounds 1-5, for A/B runs)
-
-
 class _Groups:
     """Edges grouped by an integer key, through the BA's index kernels: perm / seg_start / n_seg (+ group_of scratch)."""
 
@@ -662,13 +642,12 @@ class _Groups:
         return self
 
     def _finish(self, E):
-        key = self.perm
         self._n_host, self._n_event = _pinned_word()
         self._n_host.copy_(self.n_seg_dev, non_blocking=True)
         self._n_event.record()
         self._n_seg = None
         self.n_edges = E
-        self.group_of = torch.empty(E, dtype=torch.int32, device=key.device)
+        self.group_of = torch.empty(E, dtype=torch.int32, device=self.perm.device)
         self._group_of_long = None
 
     @property
@@ -686,7 +665,6 @@ class _Groups:
         if self._n_seg is None and self._n_event.query():
             self._n_seg = int(self._n_host[0])
         return self._n_seg if self._n_seg is not None else self.n_edges
-
 
     def group_of_long(self):
         """edge -> group index as int64 (for index_select in the training path), from the tables themselves"""
@@ -709,6 +687,23 @@ def _ln(x, mod, add1=None, add2=None, expand=None, gated=None, relu=False):
                                     x.shape[0], x.shape[1], float(mod.eps), int(relu), L.dtype_code(x), L.stream())
     L.check(rc, "update.layernorm")
     return out
+
+
+def _rs_rows_ok(dt, dim):
+    """the operator's rows fit the row-resident chain kernels of csrc/gemm_rs.hip: fp16 storage, 384 wide (the switches are read per call)"""
+    return RS_CHAINS and RS_GEMM and dt == torch.float16 and dim == 384
+
+
+def _rs_chain_ok(dt, dim, x, inp2, c):
+    """this call can take the whole row-resident chain (Update._forward_rs): a correlation width of 769 - 896 in 4-byte aligned rows, the
+    state x and the context inp2 16-byte aligned"""
+    return (_rs_rows_ok(dt, dim) and 768 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0 and c.data_ptr() % 4 == 0
+            and inp2.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
+
+
+# the usual edges per group of the two aggregations (a patch's trajectory, a frame pair's patches): picks the SoftAgg kernel's workgroup
+# shape while a new graph's group count is still on its way to the host
+AGG_ROWS_HINT = {"agg_kk": 16, "agg_ij": 96}
 
 
 class Update(nn.Module):
@@ -778,26 +773,16 @@ class Update(nn.Module):
         and handed to another tensor, so an equal key means the very same storage, and in-place edits bump the version
         counter.  (DEVO rebuilds ii / jj / kk with torch.cat every frame: fresh tensors -> rebuilt tables.)"""
         key = (ii.data_ptr(), jj.data_ptr(), kk.data_ptr(), ii._version, jj._version, kk._version, ii.numel(), jj.numel(), kk.numel())
-        if key != self._graph_key and ii.numel() and _GRAPH_TABLES:
-            # one library call (round 6, devo_upd_graph_tables): the patch groups, the neighbours read off them, the pair key and its groups
-            ix, jx, tk, tp = cuda_ba.graph_tables(ii, jj, kk)
+        if key != self._graph_key:
             E = kk.numel()
-            self._graph = (ix, jx, _Groups.from_tables(tk, E), _Groups.from_tables(tp, E))
-            self._graph_key = key
-            self._graph_refs = (ii, jj, kk)
-        elif key != self._graph_key:
-            ix, jx = cuda_ba.neighbors(kk, jj)
-            il, jl = ii.long(), jj.long()
-            # frame-pair key compacted to the window of live frames ON THE DEVICE (round 6: the bounds never visit the host — this runs once per
-            # graph, i.e. once per frame in DEVO's steady state, and the .tolist() stalled the eager pipeline): (ii - min ii) * span + (jj - min jj)
-            # with span = max jj - min jj + 1 as a 0-d tensor — the same groups as ii * 12345 + jj (enet.py:94), keys in a range of
-            # (frames in the window)^2, which is what the index kernels' flag / scan passes walk
             if ii.numel():
-                jmin = jl.min()
-                pair = ((il - il.min()) * (jl.max() - jmin + 1) + (jl - jmin)).contiguous()
-            else:
-                pair = il
-            self._graph = (ix, jx, _Groups(kk.long().contiguous()), _Groups(pair))
+                # one library call (devo_upd_graph_tables): the patch groups, the neighbours read off them, the pair key and its groups
+                ix, jx, tk, tp = cuda_ba.graph_tables(ii, jj, kk)
+                Gkk, Gij = _Groups.from_tables(tk, E), _Groups.from_tables(tp, E)
+            else:                                                            # (no edges: that call refuses them; the index kernels' empty tables)
+                ix, jx = cuda_ba.neighbors(kk, jj)
+                Gkk, Gij = _Groups(kk.long().contiguous()), _Groups(ii.long())
+            self._graph = (ix, jx, Gkk, Gij)
             self._graph_key = key
             self._graph_refs = (ii, jj, kk)                                  # keep the key's storages alive (see above)
         return self._graph
@@ -808,9 +793,10 @@ class Update(nn.Module):
         self.invalidate_weights()
 
     def _rs_plan(self):
-        """Everything the fp16 row-resident path hands to its ten launches — weight images, bias / LayerNorm vectors as raw pointers, the
-        epsilons — collected once per version of the parameters: the eager call is host-bound otherwise (39 nn.Sequential lookups, 120
-        parameter lookups and 60 pointer conversions per call: 185 us where the GPU needs 230)."""
+        """Everything the fp16 operator hands to its row-resident launches (the ten of _forward_rs; the f | g and "gru" tails of the layer-wise
+        path) — weight images, bias / LayerNorm vectors as raw pointers, the epsilons — collected once per version of the parameters: the
+        eager call is host-bound otherwise (39 nn.Sequential lookups, 120 parameter lookups and 60 pointer conversions per call: 185 us
+        where the GPU needs 230).  "ok": every vector meets the kernels' alignments (always, for storage torch allocated)."""
         key = self._pkey()
         pl = self.__dict__.get("_rsplan")
         if pl is not None and pl["key"] == key:
@@ -835,7 +821,7 @@ class Update(nn.Module):
                   c1=(im(self.c1[0].weight), P(self.c1[0].bias), im(self.c1[2].weight), P(self.c1[2].bias)),
                   c2=(im(self.c2[0].weight), P(self.c2[0].bias), im(self.c2[2].weight), P(self.c2[2].bias)),
                   fg_kk=(im(Wkk), P(bkk)), fg_ij=(im(Wij), P(bij)),
-                  h_kk=(im(self.agg_kk.h.weight), P(self.agg_kk.h.bias)), h_ij=(im(self.agg_ij.h.weight), P(self.agg_ij.h.bias)),
+                  agg_kk=(im(self.agg_kk.h.weight), P(self.agg_kk.h.bias)), agg_ij=(im(self.agg_ij.h.weight), P(self.agg_ij.h.bias)),
                   gru=(P(g[0].weight), P(g[0].bias), float(g[0].eps), im(W1), P(b1), im(g[1].res[2].weight), P(g[1].res[2].bias), P(g[2].weight),
                        P(g[2].bias), float(g[2].eps), im(W3), P(b3), im(g[3].res[2].weight), P(g[3].res[2].bias), P(self.d[1].weight), P(self.d[1].bias),
                        P(self.w[1].weight), P(self.w[1].bias)))
@@ -894,25 +880,22 @@ class Update(nn.Module):
         x = y
         code = L.dtype_code(x)
 
-        def agg(G, h, hint):
-            # (a graph seen for the first time: the group count may still be on its way to the host — rows() does not wait for it; `hint` = the
-            #  usual rows per group of this aggregation, which only picks the kernel's workgroup shape)
-            rows = G.rows()
+        def agg(G, name):
+            # (a graph seen for the first time: the group count may still be on its way to the host — rows() does not wait for it)
+            rows, h = G.rows(), pl[name]                         # (h: the image and the bias of the aggregation's h layer)
             ys = torch.empty(rows, dim, dtype=dt, device=dev)
             chk(lib.devo_upd_softagg_hint(P(fg), P(fg[:, dim:]), 2 * dim, P(G.perm), P(G.seg_start), P(G.n_seg_dev), P(ys), P(G.group_of), E, dim, code,
-                                          (E // max(rows, 1)) if rows < E else hint, st), "update.softagg")
+                                          (E // max(rows, 1)) if rows < E else AGG_ROWS_HINT[name], st), "update.softagg")
             hy = torch.empty(rows, dim, dtype=dt, device=dev)
             chk(lib.devo_upd_rs_linear_f16(P(ys), dim, h[0], h[1], None, P(hy), dim, rows, dim, dim, dim, st), "update.rs_linear_f16")
             return hy
-        hy = agg(Gkk, pl["h_kk"], 16)
+        hy = agg(Gkk, "agg_kk")
         chk(lib.devo_upd_rs_expand_fg_f16(P(x), P(hy), P(Gkk.group_of), *pl["fg_ij"], P(fg), E, st), "update.rs_expand_fg_f16")
-        hy = agg(Gij, pl["h_ij"], 96)
+        hy = agg(Gij, "agg_ij")
         net_out = torch.empty(E, dim, dtype=torch.float32 if net32 else dt, device=dev)
         dw = torch.empty(2, E, 2, dtype=dt, device=dev)
-        g = pl["gru"]
         gru_fn = lib.devo_upd_rs_gru_f16_out32 if net32 else lib.devo_upd_rs_gru_f16
-        chk(gru_fn(P(x), P(hy), P(Gij.group_of), g[0], g[1], g[2], g[3], g[4], g[5], g[6], g[7], g[8], g[9], g[10], g[11], g[12], g[13],
-                                    g[14], g[15], g[16], g[17], P(net_out), P(dw[0]), P(dw[1]), E, st), "update.rs_gru_f16")
+        chk(gru_fn(P(x), P(hy), P(Gij.group_of), *pl["gru"], P(net_out), P(dw[0]), P(dw[1]), E, st), "update.rs_gru_f16")
         return net_out.view(1, E, dim), (dw[0].view(1, E, 2), dw[1].view(1, E, 2), None)
 
     def _forward_mixed(self, net, inp, corr, flow, ii, jj, kk):
@@ -921,19 +904,16 @@ class Update(nn.Module):
         state in fp32 — two conversion passes over [E, 384] less per call (34 us of the 45 312-edge steady-state frame); anything else:
         the fp16 operator between explicit conversions."""
         B, E, dim = net.shape
-        if (B == 1 and E > 0 and MIXED_STATE and net.dtype == torch.float32 and net.is_cuda and RS_CHAINS and RS_GEMM and dim == 384
-                and self.norm.weight.dtype == torch.float16):
-            x = net.reshape(E, dim)
-            x = x if x.is_contiguous() else x.contiguous()
-            inp2, c = inp.reshape(E, dim).half().contiguous(), corr.reshape(E, -1).half()
-            if (768 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0 and c.data_ptr() % 4 == 0 and inp2.data_ptr() % 16 == 0
-                    and x.data_ptr() % 16 == 0):
+        inp, corr = inp.half(), corr.half()
+        if B == 1 and E > 0 and MIXED_STATE and net.dtype == torch.float32 and net.is_cuda:
+            x, inp2, c = net.reshape(E, dim).contiguous(), inp.reshape(E, dim).contiguous(), corr.reshape(E, -1)
+            if _rs_chain_ok(self.norm.weight.dtype, dim, x, inp2, c):
                 L.require_gpu(net, inp, corr, ii, jj, kk)
                 ix, jx, Gkk, Gij = self._tables(ii, jj, kk)
                 fast = self._forward_rs(x, inp2, c, ix, jx, Gkk, Gij, E, net32=True)
                 if fast is not None:
                     return fast
-        n16, (d16, w16, _) = self(net.half(), inp.half(), corr.half(), flow, ii, jj, kk)
+        n16, (d16, w16, _) = self(net.half(), inp, corr, flow, ii, jj, kk)
         return n16.float(), (d16, w16, None)
 
     def _half_shadow(self):
@@ -1004,7 +984,7 @@ class Update(nn.Module):
         y = torch.empty(rows, dim, dtype=net.dtype, device=net.device)
         L.check(L.lib().devo_upd_softagg_hint(L.ptr(fg), L.ptr(fg[:, dim:]), 2 * dim, L.ptr(G.perm), L.ptr(G.seg_start), L.ptr(G.n_seg_dev),
                                               L.ptr(y), L.ptr(G.group_of), E, dim, L.dtype_code(net),
-                                              int(E // max(rows, 1)) if rows < E else (16 if name == "agg_kk" else 96), L.stream()),
+                                              int(E // max(rows, 1)) if rows < E else AGG_ROWS_HINT[name], L.stream()),
                 "update.softagg")
         return F.linear(y, agg.h.weight, agg.h.bias), G.group_of
 
@@ -1047,47 +1027,41 @@ class Update(nn.Module):
             with torch.autocast("cuda", enabled=False):
                 return self.forward(net, inp, corr, flow, ii, jj, kk)
         x, inp2, c = net.reshape(E, dim).to(dt).contiguous(), inp.reshape(E, dim).to(dt).contiguous(), corr.reshape(E, -1).to(dt)
-        lib, code = L.lib(), L.dtype_code(x)
+        lib, code, P, st = L.lib(), L.dtype_code(x), L.ptr, L.stream()
         ix, jx, Gkk, Gij = self._tables(ii, jj, kk)
-        if (RS_CHAINS and RS_GEMM and dt == torch.float16 and dim == 384 and 768 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0
-                and c.data_ptr() % 4 == 0 and inp2.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
+        if _rs_chain_ok(dt, dim, x, inp2, c):
             fast = self._forward_rs(x, inp2, c, ix, jx, Gkk, Gij, E)
             if fast is not None:
                 return fast
+        # layer by layer.  A correlation width outside the chain's keeps the row-resident launches that need none of it — the f | g layers of the
+        # SoftAggs on the kernels in front of them, everything behind the aggregation — on the plan's arguments; parameters whose storage
+        # misses the plan's alignments (views into a larger buffer) take the unfused forms throughout
+        pl = self._rs_plan() if _rs_rows_ok(dt, dim) else None
+        tails = pl is not None and pl["ok"]
 
         # corr MLP (enet.py:59-66) and net = norm(net + inp + corr)  (:82-83), the two adds fused into the LayerNorm
-        if (RS_CHAINS and RS_GEMM and dt == torch.float16 and dim == 384 and 768 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0
-                and c.data_ptr() % 4 == 0 and inp2.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0):
-            # the whole correlation branch and norm(net + inp + corr) in ONE launch, rows in LDS (csrc/gemm_rs.hip)
-            out = torch.empty_like(x)
-            L.check(lib.devo_upd_rs_corr_f16(L.ptr(c), c.stride(0), c.shape[1], L.ptr(_rs_image(self.corr[0].weight.detach())), L.ptr(self.corr[0].bias),
-                                             L.ptr(_rs_image(self.corr[2].weight.detach())), L.ptr(self.corr[2].bias), L.ptr(self.corr[3].weight),
-                                             L.ptr(self.corr[3].bias), float(self.corr[3].eps), L.ptr(_rs_image(self.corr[5].weight.detach())),
-                                             L.ptr(self.corr[5].bias), L.ptr(x), L.ptr(inp2), L.ptr(self.norm.weight), L.ptr(self.norm.bias),
-                                             float(self.norm.eps), L.ptr(out), E, L.stream()), "update.rs_corr_f16")
-            x, c = out, None
-        elif _mlp2_ok(c, self.corr[0], self.corr[2]):                 # Linear - ReLU - Linear: one launch, the intermediate stays in LDS
+        if _mlp2_ok(c, self.corr[0], self.corr[2]):                   # Linear - ReLU - Linear: one launch, the intermediate stays in LDS
             c = _mlp2_f16(c, self.corr[0], self.corr[2])
         else:
             c = self._lin(c, self.corr[0].weight, self.corr[0].bias, relu=True)
             c = self._lin(c, self.corr[2].weight, self.corr[2].bias)
-        if c is not None:
-            c = _ln(c, self.corr[3], relu=True)
-            c = self._lin(c, self.corr[5].weight, self.corr[5].bias)
-            x = _ln(x, self.norm, add1=inp2, add2=c)
+        c = _ln(c, self.corr[3], relu=True)
+        c = self._lin(c, self.corr[5].weight, self.corr[5].bias)
+        x = _ln(x, self.norm, add1=inp2, add2=c)
 
         # neighbour mixing along the patch trajectory (:86-91)
-        tails = RS_CHAINS and RS_GEMM and dt == torch.float16 and dim == 384     # the SoftAgg's f | g layers ride on the kernels in front of them
         fg_kk = None
         for mlp, idx in ((self.c1, ix), (self.c2, jx)):
             if _mlp2_ok(x, mlp[0], mlp[2]) and x.is_contiguous():
-                if tails and mlp is self.c2:
-                    x, fg_kk = _mlp2_f16(x, mlp[0], mlp[2], residual=x, gather=idx, fg=self._cat("agg_kk", self.agg_kk.f, self.agg_kk.g))
+                if tails and mlp is self.c2:                          # ... and agg_kk's f | g layer on the result rows while they are in LDS
+                    y, fg_kk = torch.empty_like(x), torch.empty(E, 2 * dim, dtype=dt, device=x.device)
+                    L.check(lib.devo_upd_rs_mlp2_fg_f16(P(x), dim, E, P(idx), *pl["c2"], P(x), P(y), E, *pl["fg_kk"], P(fg_kk), st), "update.rs_mlp2_f16")
+                    x = y
                     continue
                 x = _mlp2_f16(x, mlp[0], mlp[2], residual=x, gather=idx)     # net + c(mask * net[:, idx]): gather, both layers and the sum in one launch
                 continue
             t = torch.empty_like(x)
-            L.check(lib.devo_upd_masked_gather(L.ptr(x), L.ptr(idx), L.ptr(t), E, dim, code, L.stream()), "update.masked_gather")
+            L.check(lib.devo_upd_masked_gather(P(x), P(idx), P(t), E, dim, code, st), "update.masked_gather")
             t = self._lin(t, mlp[0].weight, mlp[0].bias, relu=True)
             self._lin(t, mlp[2].weight, mlp[2].bias, residual=x)     # x += c(t)
 
@@ -1095,38 +1069,22 @@ class Update(nn.Module):
         # fused into the LayerNorm of the "gru" (:52-57), and each GatedResidual into the op that consumes it
         hy, grp = self._soft_agg("agg_kk", self.agg_kk, x, Gkk, fg=fg_kk)
         if tails and x.is_contiguous() and hy.is_contiguous() and x.data_ptr() % 16 == 0:
-            Wij, bij = self._cat("agg_ij", self.agg_ij.f, self.agg_ij.g)     # x += hy[grp] and agg_ij's f | g layer on the same rows: one launch
-            fg_ij = torch.empty(E, 2 * dim, dtype=dt, device=x.device)
-            L.check(lib.devo_upd_rs_expand_fg_f16(L.ptr(x), L.ptr(hy), L.ptr(grp), L.ptr(_rs_image(Wij)), L.ptr(bij), L.ptr(fg_ij), E, L.stream()),
-                    "update.rs_expand_fg_f16")
+            fg_ij = torch.empty(E, 2 * dim, dtype=dt, device=x.device)       # x += hy[grp] and agg_ij's f | g layer on the same rows: one launch
+            L.check(lib.devo_upd_rs_expand_fg_f16(P(x), P(hy), P(grp), *pl["fg_ij"], P(fg_ij), E, st), "update.rs_expand_fg_f16")
             hy, grp = self._soft_agg("agg_ij", self.agg_ij, x, Gij, fg=fg_ij)
         else:
-            L.check(lib.devo_upd_expand_add(L.ptr(x), L.ptr(hy), L.ptr(grp), E, dim, code, L.stream()), "update.expand_add")
+            L.check(lib.devo_upd_expand_add(P(x), P(hy), P(grp), E, dim, code, st), "update.expand_add")
             hy, grp = self._soft_agg("agg_ij", self.agg_ij, x, Gij)
-        if RS_CHAINS and dt == torch.float16 and dim == 384 and RS_GEMM and x.is_contiguous() and hy.is_contiguous():
-            # everything behind the aggregation is row-local: both LayerNorms, both GatedResiduals and the heads in ONE launch, rows in LDS
-            net_out = torch.empty_like(x)
-            delta = torch.empty(E, 2, dtype=dt, device=x.device)
-            weight = torch.empty(E, 2, dtype=dt, device=x.device)
-            W1, b1 = self._cat("gru1", self.gru[1].gate[0], self.gru[1].res[0])
-            W3, b3 = self._cat("gru3", self.gru[3].gate[0], self.gru[3].res[0])
-            r1, r3 = self.gru[1].res[2], self.gru[3].res[2]
-            L.check(lib.devo_upd_rs_gru_f16(L.ptr(x), L.ptr(hy), L.ptr(grp), L.ptr(self.gru[0].weight), L.ptr(self.gru[0].bias), float(self.gru[0].eps),
-                                            L.ptr(_rs_image(W1)), L.ptr(b1), L.ptr(_rs_image(r1.weight.detach())), L.ptr(r1.bias), L.ptr(self.gru[2].weight),
-                                            L.ptr(self.gru[2].bias), float(self.gru[2].eps), L.ptr(_rs_image(W3)), L.ptr(b3),
-                                            L.ptr(_rs_image(r3.weight.detach())), L.ptr(r3.bias), L.ptr(self.d[1].weight), L.ptr(self.d[1].bias),
-                                            L.ptr(self.w[1].weight), L.ptr(self.w[1].bias), L.ptr(net_out), L.ptr(delta), L.ptr(weight), E, L.stream()),
-                    "update.rs_gru_f16")
-            return net_out.view(1, E, dim), (delta.view(1, E, 2), weight.view(1, E, 2), None)
-        x = _ln(x, self.gru[0], expand=(hy, grp))                                  # LN(net + agg_ij(net))
-        x = _ln(x, self.gru[2], gated=self._gate_res("gru1", self.gru[1], x))     # LN(GatedResidual(.))
-        gate, res = self._gate_res("gru3", self.gru[3], x)
-
         net_out = torch.empty_like(x)
         delta = torch.empty(E, 2, dtype=dt, device=x.device)
         weight = torch.empty(E, 2, dtype=dt, device=x.device)
-        L.check(lib.devo_upd_heads(L.ptr(x), L.ptr(gate), gate.stride(0), L.ptr(res), L.ptr(net_out), L.ptr(self.d[1].weight),
-                                   L.ptr(self.d[1].bias), L.ptr(self.w[1].weight), L.ptr(self.w[1].bias), L.ptr(delta), L.ptr(weight),
-                                   E, dim, code, L.stream()), "update.heads")
-        x = net_out
-        return x.view(1, E, dim), (delta.view(1, E, 2), weight.view(1, E, 2), None)
+        if tails and x.is_contiguous() and hy.is_contiguous():
+            # everything behind the aggregation is row-local: both LayerNorms, both GatedResiduals and the heads in ONE launch, rows in LDS
+            L.check(lib.devo_upd_rs_gru_f16(P(x), P(hy), P(grp), *pl["gru"], P(net_out), P(delta), P(weight), E, st), "update.rs_gru_f16")
+        else:
+            x = _ln(x, self.gru[0], expand=(hy, grp))                                  # LN(net + agg_ij(net))
+            x = _ln(x, self.gru[2], gated=self._gate_res("gru1", self.gru[1], x))     # LN(GatedResidual(.))
+            gate, res = self._gate_res("gru3", self.gru[3], x)
+            L.check(lib.devo_upd_heads(P(x), P(gate), gate.stride(0), P(res), P(net_out), P(self.d[1].weight), P(self.d[1].bias),
+                                       P(self.w[1].weight), P(self.w[1].bias), P(delta), P(weight), E, dim, code, st), "update.heads")
+        return net_out.view(1, E, dim), (delta.view(1, E, 2), weight.view(1, E, 2), None)
