@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.environ["DEVO_LIB"]) if os.environ.get("DEVO_LIB") else os.path.join(_HERE, "lib", "libdevo_hip.so")
 
 DEVO_F32, DEVO_F16, DEVO_F64 = 0, 1, 2
-ABI_VERSION = 8                # include/devo_hip.h DEVO_ABI_VERSION: a library of another version is refused (argument lists differ)
+ABI_VERSION = 9                # include/devo_hip.h DEVO_ABI_VERSION: a library of another version is refused (argument lists differ)
 CBLOCK_SPLIT8 = -8             # DEVO_CBLOCK_SPLIT8: fp32 level in the split-blocked format of devo_corr_pyramid_split
 PLAN_TAIL = 4104               # DEVO_CORR_PLAN_TAIL: a plan buffer that can hold a group plan has 2 n + 2 + PLAN_TAIL ints
 PLAN_EDGES, PLAN_GROUPS = 0, 1
@@ -127,6 +127,15 @@ _SIGNATURES.update({
     "devo_depth_normalise_workspace_bytes": [_i],
     "devo_depth_normalise": [_vp, _i64, _i, _vp, _i, _i, _f, _f, _vp, _vp, _sz, _vp],
 })
+_d = ctypes.c_double
+_SIGNATURES.update({
+    "devo_graph_workspace_bytes": [_i],
+    "devo_graph_motion": [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _f, _vp, _sz, _vp, _vp],
+    "devo_graph_keyframe": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i64, _i, _i, _i, _i, _i, _i, _d, _i, _f, _vp, _sz, _vp, _vp],
+    "devo_graph_remove": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp, _sz, _vp, _vp],
+    "devo_graph_append": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "devo_graph_shift_frames": [ctypes.POINTER(ctypes.c_void_p), _c_i64p, _i, _i, _i, _vp],
+})
 for _n in ("exp", "log", "inv"):
     _SIGNATURES[f"devo_se3_{_n}"] = [_vp, _vp, _i64, _i, _vp]
     _SIGNATURES[f"devo_se3_{_n}_backward"] = [_vp, _vp, _vp, _i64, _i, _vp]
@@ -137,7 +146,7 @@ _SIGNATURES["devo_se3_as_matrix"] = [_vp, _vp, _i64, _i, _vp]
 _SIGNATURES["devo_se3_jinv"] = [_vp, _vp, _vp, _i64, _i, _vp]
 _RESTYPE = {"devo_last_error": ctypes.c_char_p, "devo_instnorm_workspace_bytes": _sz, "devo_voxel_std_workspace_bytes": _sz, "devo_voxelize_windows_workspace_bytes": _sz,
              "devo_voxel_hot_pixels_workspace_bytes": _sz, "devo_voxel_rescale_workspace_bytes": _sz, "devo_voxel_augment_workspace_bytes": _sz, "devo_depth_normalise_workspace_bytes": _sz, "devo_ba_workspace_bytes": _sz, "devo_neighbors_workspace_bytes": _sz,
-             "devo_corr_backward_workspace_bytes": _sz, "devo_corr_patch_operand_bytes": _sz, "devo_upd_split_weight_bytes": _sz, "devo_upd_dw_workspace_bytes": _sz, "devo_upd_pack_weight_f16_bytes": _sz, "devo_upd_mlp2_weight_bytes": _sz, "devo_upd_rs_weight_bytes": _sz, "devo_upd_rs_split_weight_bytes": _sz}
+             "devo_corr_backward_workspace_bytes": _sz, "devo_corr_patch_operand_bytes": _sz, "devo_upd_split_weight_bytes": _sz, "devo_upd_dw_workspace_bytes": _sz, "devo_upd_pack_weight_f16_bytes": _sz, "devo_upd_mlp2_weight_bytes": _sz, "devo_upd_rs_weight_bytes": _sz, "devo_upd_rs_split_weight_bytes": _sz, "devo_graph_workspace_bytes": _sz}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

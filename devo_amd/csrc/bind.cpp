@@ -619,6 +619,78 @@ c10::optional<Tensor> corr_patch_operand(Tensor fmap1) {
   const Tensor t = patch_operand(fmap1.contiguous());
   return t.defined() ? c10::optional<Tensor>(t) : c10::nullopt;
 }
+// ------------------------------------------------------------------------------------------------ patch graph (devo_amd/graph.py; csrc/graph.hip)
+// Thin forms of the devo_graph_* entry points: tensors for pointers, the current stream of the index tensors' device.  `record` is a pinned
+// HOST tensor the kernels write (devo_hip.h); the Python class owns the buffers, the event and the version counters.
+const int64_t* i64p(const Tensor& t) { return t.data_ptr<int64_t>(); }
+void pg_check_idx(const char* what, const Tensor& t) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous(), what, ": index tensors must be contiguous int64 tensors on the GPU");
+}
+void pg_geometry(const char* what, const Tensor& poses, const Tensor& patches, const Tensor& intrinsics) {
+  require_gpu(poses, patches, intrinsics);
+  TORCH_CHECK(poses.scalar_type() == at::kFloat && poses.is_contiguous() && patches.scalar_type() == at::kFloat && patches.is_contiguous() &&
+              intrinsics.scalar_type() == at::kFloat && intrinsics.is_contiguous(), what, ": poses, patches and intrinsics must be contiguous float32 tensors");
+}
+
+void pg_motion(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ii, Tensor jj, Tensor kk, int64_t E, int64_t i, int64_t j, double beta, Tensor ws, Tensor record) {
+  pg_geometry("patch_graph.motion", poses, patches, intrinsics);
+  pg_check_idx("patch_graph.motion", ii); pg_check_idx("patch_graph.motion", jj); pg_check_idx("patch_graph.motion", kk);
+  c10::DeviceGuard guard(ii.device());
+  const int64_t P = patches.size(-1);
+  check(devo_graph_motion(poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(), i64p(ii), i64p(jj), i64p(kk), (int)E, (int)(poses.numel() / 7),
+                          (int)(patches.numel() / (3 * P * P)), (int)P, (int)i, (int)j, (float)beta, ws.data_ptr(), (size_t)ws.numel(), record.data_ptr(), stream_of(ii)),
+        "patch_graph.motion");
+}
+
+void pg_keyframe(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ii, Tensor jj, Tensor kk, Tensor net, Tensor ix, Tensor ii_out, Tensor jj_out, Tensor kk_out,
+                 Tensor net_out, int64_t E, int64_t M, int64_t n, int64_t keyframe_index, double thresh, int64_t removal_window, double beta, Tensor ws, Tensor record) {
+  pg_geometry("patch_graph.keyframe", poses, patches, intrinsics);
+  for (const Tensor* t : {&ii, &jj, &kk, &ix, &ii_out, &jj_out, &kk_out}) pg_check_idx("patch_graph.keyframe", *t);
+  require_gpu(net, net_out);
+  c10::DeviceGuard guard(ii.device());
+  const int64_t P = patches.size(-1);
+  check(devo_graph_keyframe(poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(), i64p(ii), i64p(jj), i64p(kk), net.data_ptr(), i64p(ix),
+                            ii_out.data_ptr<int64_t>(), jj_out.data_ptr<int64_t>(), kk_out.data_ptr<int64_t>(), net_out.data_ptr(), (int)E, (int)(poses.numel() / 7),
+                            (int)(patches.numel() / (3 * P * P)), ix.numel(), (int)P, (int)net.size(-1), dtype_code(net), (int)M, (int)n, (int)keyframe_index, thresh,
+                            (int)removal_window, (float)beta, ws.data_ptr(), (size_t)ws.numel(), record.data_ptr(), stream_of(ii)), "patch_graph.keyframe");
+}
+
+void pg_remove(Tensor ii, Tensor jj, Tensor kk, Tensor net, Tensor mask, Tensor ii_out, Tensor jj_out, Tensor kk_out, Tensor net_out, int64_t E, Tensor ws, Tensor record) {
+  for (const Tensor* t : {&ii, &jj, &kk, &ii_out, &jj_out, &kk_out}) pg_check_idx("patch_graph.remove", *t);
+  require_gpu(net, net_out, mask);
+  TORCH_CHECK((mask.scalar_type() == at::kBool || mask.scalar_type() == at::kByte) && mask.is_contiguous(), "patch_graph.remove: the mask must be a contiguous bool tensor");
+  c10::DeviceGuard guard(ii.device());
+  check(devo_graph_remove(i64p(ii), i64p(jj), i64p(kk), net.data_ptr(), (const unsigned char*)mask.data_ptr(), ii_out.data_ptr<int64_t>(), jj_out.data_ptr<int64_t>(),
+                          kk_out.data_ptr<int64_t>(), net_out.data_ptr(), (int)E, (int)net.size(-1), dtype_code(net), ws.data_ptr(), (size_t)ws.numel(), record.data_ptr(),
+                          stream_of(ii)), "patch_graph.remove");
+}
+
+void pg_append(Tensor ii, Tensor jj, Tensor kk, Tensor net_old, Tensor net_new, Tensor ix, Tensor patch_ids, Tensor frame_ids, int64_t E, int64_t n_new) {
+  for (const Tensor* t : {&ii, &jj, &kk, &ix, &patch_ids, &frame_ids}) pg_check_idx("patch_graph.append", *t);
+  require_gpu(net_old, net_new);
+  c10::DeviceGuard guard(ii.device());
+  check(devo_graph_append(ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), net_old.data_ptr(), net_new.data_ptr(), i64p(ix), ix.numel(), i64p(patch_ids),
+                          i64p(frame_ids), (int)E, (int)n_new, (int)ii.numel(), (int)net_new.size(-1), dtype_code(net_new), stream_of(ii)), "patch_graph.append");
+}
+
+void pg_shift_frames(TensorList tensors, int64_t k, int64_t n) {
+  if (tensors.empty()) return;
+  std::vector<void*> ptrs;
+  std::vector<int64_t> rows;
+  for (const Tensor& t : tensors) {
+    require_gpu(t);
+    TORCH_CHECK(t.dim() >= 1 && t.is_contiguous() && t.size(0) >= n && t.device() == tensors[0].device(), "patch_graph.shift_frames: contiguous tensors of at least n rows on one device");
+    ptrs.push_back(t.data_ptr());
+    rows.push_back(t.size(0) ? (int64_t)(t.numel() / t.size(0) * t.element_size()) : 0);
+  }
+  c10::DeviceGuard guard(tensors[0].device());
+  check(devo_graph_shift_frames(ptrs.data(), rows.data(), (int)ptrs.size(), (int)k, (int)n, stream_of(tensors[0])), "patch_graph.shift_frames");
+}
+
+// a kernel wrote the tensor through its raw pointer: what an in-place ATen operation would have done to the version counter (shared by every
+// view of the storage), so that the version-keyed caches above and devo_amd.update's graph tables see the write.  No launch.
+void bump_version(Tensor t) { t.unsafeGetTensorImpl()->bump_version(); }
+
 void clear_caches() {
   g_levels.clear(); g_patches.clear(); g_cl.clear();
   g_last_plan = LastPlan();
@@ -716,6 +788,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ba.def("reproject", &ba_reproject, "ba.cpp:155");
   ba.def("transform_coords", &ba_transform, py::arg("poses"), py::arg("patches"), py::arg("intrinsics"), py::arg("ii"), py::arg("jj"), py::arg("kk"),
          py::arg("layout_2pp") = false);
+
+  auto pg = m.def_submodule("patch_graph", "devo_amd.graph: devo/devo.py:225-239, :258-306 on the graph");
+  pg.def("motion", &pg_motion);
+  pg.def("keyframe", &pg_keyframe);
+  pg.def("remove", &pg_remove);
+  pg.def("append", &pg_append);
+  pg.def("shift_frames", &pg_shift_frames);
+  pg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_graph_workspace_bytes((int)capacity); });
+  m.def("bump_version", &bump_version, "count a raw-pointer write as an in-place edit of the tensor (no launch)");
 
   auto lie = m.def_submodule("lietorch_backends", "devo/lietorch/src/lietorch.cpp:286-316 (SE3)");
   lie.def("expm", &lie_unary<devo_se3_exp, 7>);

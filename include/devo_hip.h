@@ -27,12 +27,13 @@ typedef void* devo_stream_t; /* hipStream_t */
 enum { DEVO_OK = 0, DEVO_ERR_ARG = 1, DEVO_ERR_LAUNCH = 2, DEVO_ERR_UNSUPPORTED = 3, DEVO_ERR_WORKSPACE = 4 };
 enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
 
-#define DEVO_ABI_VERSION 8 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
+#define DEVO_ABI_VERSION 9 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
                               (devo_corr_pyramid_split_frames, devo_corr_patch_transpose_range), devo_stream_capturing; 4: devo_ba_table_offsets, devo_upd_graph_tables; 5: devo_ba_forward_prepared_delta_plan, devo_ba_import_tables, devo_upd_rs_corr_f16_net32,
                               devo_upd_rs_gru_f16_out32, devo_instnorm_cl, devo_instnorm_bias_cl, devo_bias_act_cl;
                               6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
                               7: devo_voxel_augment, devo_voxel_augment_workspace_bytes;
                               8: devo_voxel_resample, devo_depth_normalise, devo_depth_normalise_workspace_bytes;
+                              9: devo_graph_motion, devo_graph_keyframe, devo_graph_remove, devo_graph_append, devo_graph_shift_frames, devo_graph_workspace_bytes;
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -660,6 +661,53 @@ int devo_voxel_resample(const float* src, float* dst, int B, int C, int H, int W
 size_t devo_depth_normalise_workspace_bytes(int B);
 int devo_depth_normalise(float* disps, int64_t n, int B, float* poses, int P, int pose_stride, float q, float factor, float* s_out, void* ws,
                          size_t ws_bytes, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The patch graph of DEVO's inference (devo/devo.py:225-239 append_factors / remove_factors, :258-265 motionmag, :267-306 keyframe):
+ * edge lists ii (source frame), jj (target frame), kk (patch) i64 [E] and the recurrent state net T [1, E, dim] (fp16 or fp32, dim a
+ * multiple of 8, 16-byte aligned: rows move as 16-byte words).  ws: devo_graph_workspace_bytes(capacity) serves every call on a
+ * graph of up to `capacity` edges; calls that share a workspace must be enqueued on one stream.  `record` is a HOST-VISIBLE word
+ * (pinned host memory, device-addressable at its own address) of DEVO_GRAPH_RECORD_BYTES = {i32 removed, i32 n_edges, f32 mean_ij,
+ * f32 mean_ji}, written by the last kernel of the call; the caller records an event behind the call and waits for that.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_GRAPH_RECORD_BYTES 16
+#define DEVO_GRAPH_SHIFT_MAX 8
+size_t devo_graph_workspace_bytes(int capacity);
+
+/* motionmag(i, j) and motionmag(j, i) (devo.py:258-265) in one pass over all edges: the mean of pops.flow_mag(beta) over the edges
+ * with (ii, jj) == (i, j) -> record.mean_ij, over those with (ii, jj) == (j, i) -> record.mean_ji; NaN where there is no such edge.
+ * poses f32 [n_poses, 7], patches f32 [n_patches, 3, P, P], intrinsics f32 [n_poses, 4]; an edge whose indices fall outside them
+ * is skipped.  Reproducible from run to run (no float atomics).  record.removed = 0, record.n_edges = E. */
+int devo_graph_motion(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj, const int64_t* kk, int E,
+                      int n_poses, int n_patches, int P, int i, int j, float beta, void* ws, size_t ws_bytes, void* record, devo_stream_t stream);
+
+/* The graph half of DEVO.keyframe (devo.py:267-287, :305-306) with the decision taken on the device: k = n - keyframe_index,
+ * m = double(motionmag(k - 1, k + 1)) + double(motionmag(k + 1, k - 1)); if m / 2 < thresh (false for NaN) the edges with ii == k or
+ * jj == k are dropped, the survivors renumbered (kk -= M where ii > k, then ii -= 1; jj -= 1 where jj > k) and n' = n - 1, else
+ * n' = n; then the edges with ix[kk] < n' - removal_window go (kk as renumbered; ix i64 [ix_len], a kk outside it keeps its edge).
+ * Survivors keep their order (a stable compaction) and land in ii_out / jj_out / kk_out / net_out, which must hold E entries / rows
+ * and must not alias the inputs.  record: {removed, number of survivors, mean_ij, mean_ji}. */
+int devo_graph_keyframe(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj, const int64_t* kk,
+                        const void* net, const int64_t* ix, int64_t* ii_out, int64_t* jj_out, int64_t* kk_out, void* net_out, int E, int n_poses,
+                        int n_patches, int64_t ix_len, int P, int dim, int net_dtype, int M, int n, int keyframe_index, double thresh,
+                        int removal_window, float beta, void* ws, size_t ws_bytes, void* record, devo_stream_t stream);
+
+/* remove_factors(mask) (devo.py:235-239): the same stable compaction with a caller's mask (u8 / bool [E], non-zero = drop).
+ * record: {0, number of survivors, 0, 0}. */
+int devo_graph_remove(const int64_t* ii, const int64_t* jj, const int64_t* kk, const void* net, const unsigned char* mask, int64_t* ii_out,
+                      int64_t* jj_out, int64_t* kk_out, void* net_out, int E, int dim, int net_dtype, void* ws, size_t ws_bytes, void* record,
+                      devo_stream_t stream);
+
+/* append_factors (devo.py:225-233), one launch: ii / jj / kk are buffers of `capacity` entries holding E edges; entries E .. E + n_new - 1
+ * become ii = ix[patch_ids] (-1 for a patch outside ix), jj = frame_ids, kk = patch_ids; net_new [E + n_new, dim] = the E rows of
+ * net_old followed by zero rows.  E + n_new > capacity is an error (nothing is launched). */
+int devo_graph_append(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old, void* net_new, const int64_t* ix, int64_t ix_len,
+                      const int64_t* patch_ids, const int64_t* frame_ids, int E, int n_new, int capacity, int dim, int net_dtype, devo_stream_t stream);
+
+/* The frame shift of keyframe removal (devo.py:289-295) for up to DEVO_GRAPH_SHIFT_MAX tensors of any dtype in one launch: tensor s
+ * is `tensors[s]` (HOST array of device pointers), contiguous, with rows of row_bytes[s] (HOST array) bytes; rows k + 1 .. n - 1 of
+ * each move down by one (row r <- row r + 1 for r = k .. n - 2, in place). */
+int devo_graph_shift_frames(void* const* tensors, const int64_t* row_bytes, int count, int k, int n, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
