@@ -687,6 +687,57 @@ void pg_shift_frames(TensorList tensors, int64_t k, int64_t n) {
   check(devo_graph_shift_frames(ptrs.data(), rows.data(), (int)ptrs.size(), (int)k, (int)n, stream_of(tensors[0])), "patch_graph.shift_frames");
 }
 
+// ------------------------------------------------------------------------------------------------ training loss (devo_amd/losses.py; csrc/loss.hip)
+// Thin forms of devo_loss_forward / devo_loss_backward: the outputs and the state are allocated here, nothing else happens on the host.
+void loss_check(const char* what, const Tensor& t, at::ScalarType dt) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == dt && t.is_contiguous(), what, ": contiguous GPU tensors of one floating dtype (fp32 or fp64)");
+}
+const void* opt_ptr(const c10::optional<Tensor>& t) { return t.has_value() && t->defined() ? t->data_ptr() : nullptr; }
+
+// -> {loss T [1], stats f32 [DEVO_LOSS_STATS], state u8}
+TensorList loss_forward(const Tensor& x, const Tensor& y, const Tensor& v, const Tensor& Gs, const Tensor& Ps, const c10::optional<Tensor>& scores,
+                        const c10::optional<Tensor>& v_full, const c10::optional<Tensor>& x_full, const c10::optional<Tensor>& y_full,
+                        const c10::optional<Tensor>& ba_weights, const c10::optional<Tensor>& kk, bool deterministic, double flow_weight, double pose_weight,
+                        double scores_weight, bool use_pose) {
+  const at::ScalarType dt = x.scalar_type();
+  for (const Tensor* t : {&x, &y, &v, &Gs, &Ps}) loss_check("losses.forward", *t, dt);
+  const bool has = scores.has_value() && scores->defined();
+  int64_t Ef = 0, n_patches = 0;
+  if (has) {
+    TORCH_CHECK(v_full && x_full && y_full && ba_weights && kk, "losses.forward: the scorer term needs v_full, x_full, y_full, ba_weights and kk");
+    for (const Tensor* t : {&*scores, &*v_full, &*x_full, &*y_full, &*ba_weights}) loss_check("losses.forward", *t, dt);
+    pg_check_idx("losses.forward", *kk);
+    Ef = kk->numel(); n_patches = scores->numel();
+    TORCH_CHECK(v_full->numel() == Ef && ba_weights->numel() == 2 * Ef && x_full->numel() == y_full->numel(), "losses.forward: the scorer term's tensors disagree in size");
+  }
+  TORCH_CHECK(x.dim() >= 3 && x.size(-1) == 2 && x.size(-2) == x.size(-3), "losses.forward: coords must be [.., P, P, 2]");
+  const int64_t P = x.size(-2), Ec = v.numel(), n = Gs.numel() / 7;
+  TORCH_CHECK(x.numel() == Ec * P * P * 2 && y.numel() == x.numel() && Ps.numel() == Gs.numel(), "losses.forward: sizes disagree");
+  TORCH_CHECK(!has || x_full->numel() == Ef * P * P * 2, "losses.forward: coords_full must be [Ef, P, P, 2]");
+  c10::DeviceGuard guard(x.device());
+  const int code = dtype_code(x);
+  const size_t bytes = devo_loss_state_bytes((int)Ec, (int)n, (int)Ef, (int)n_patches, code);
+  Tensor loss = at::empty({1}, x.options()), stats = at::empty({DEVO_LOSS_STATS}, x.options().dtype(at::kFloat));
+  Tensor state = at::empty({(int64_t)bytes}, x.options().dtype(at::kByte));
+  check(devo_loss_forward(x.data_ptr(), y.data_ptr(), v.data_ptr(), (int)Ec, (int)P, Gs.data_ptr(), Ps.data_ptr(), (int)n, opt_ptr(scores), (int)n_patches, opt_ptr(v_full),
+                          opt_ptr(x_full), opt_ptr(y_full), opt_ptr(ba_weights), has ? i64p(*kk) : nullptr, (int)Ef, deterministic ? 1 : 0, flow_weight, pose_weight,
+                          scores_weight, use_pose ? 1 : 0, loss.data_ptr(), stats.data_ptr<float>(), state.data_ptr(), bytes, code, stream_of(x)), "losses.forward");
+  return {loss, stats, state};
+}
+
+// -> {g_coords [Ec, P, P, 2], g_Gs [n, 7], g_scores [n_patches]}; an empty tensor where it was not asked for
+TensorList loss_backward(const Tensor& g, const Tensor& state, int64_t Ec, int64_t P, int64_t n, int64_t Ef, int64_t n_patches, double flow_weight, double pose_weight,
+                         double scores_weight, bool need_coords, bool need_Gs, bool need_scores) {
+  TORCH_CHECK(g.is_cuda() && g.numel() == 1 && state.is_cuda() && state.scalar_type() == at::kByte && state.is_contiguous(), "losses.backward: bad arguments");
+  c10::DeviceGuard guard(g.device());
+  const auto o = g.options();
+  Tensor gc = at::empty({need_coords ? Ec : 0, P, P, 2}, o), gG = at::empty({need_Gs ? n : 0, 7}, o), gs = at::empty({need_scores ? n_patches : 0}, o);
+  check(devo_loss_backward(g.data_ptr(), state.data_ptr(), (size_t)state.numel(), (int)Ec, (int)P, (int)n, (int)Ef, (int)n_patches, flow_weight, pose_weight, scores_weight,
+                           need_coords ? gc.data_ptr() : nullptr, need_Gs ? gG.data_ptr() : nullptr, need_scores ? gs.data_ptr() : nullptr, dtype_code(g), stream_of(g)),
+        "losses.backward");
+  return {gc, gG, gs};
+}
+
 // a kernel wrote the tensor through its raw pointer: what an in-place ATen operation would have done to the version counter (shared by every
 // view of the storage), so that the version-keyed caches above and devo_amd.update's graph tables see the write.  No launch.
 void bump_version(Tensor t) { t.unsafeGetTensorImpl()->bump_version(); }
@@ -725,6 +776,10 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("se3_adjT(int group_id, Tensor X, Tensor a) -> Tensor");
   m.def("se3_act(int group_id, Tensor X, Tensor p) -> Tensor");
   m.def("se3_act4(int group_id, Tensor X, Tensor p) -> Tensor");
+  m.def("loss_forward(Tensor x, Tensor y, Tensor v, Tensor Gs, Tensor Ps, Tensor? scores, Tensor? v_full, Tensor? x_full, Tensor? y_full, Tensor? ba_weights, Tensor? kk, "
+        "bool deterministic, float flow_weight, float pose_weight, float scores_weight, bool use_pose) -> Tensor[]");
+  m.def("loss_backward(Tensor g, Tensor state, int Ec, int P, int n, int Ef, int n_patches, float flow_weight, float pose_weight, float scores_weight, bool need_coords, "
+        "bool need_Gs, bool need_scores) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -742,6 +797,8 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("se3_adjT", &lie_binary<devo_se3_adjT, 6>);
   m.impl("se3_act", &lie_binary<devo_se3_act, 3>);
   m.impl("se3_act4", &lie_binary<devo_se3_act4, 4>);
+  m.impl("loss_forward", &loss_forward);
+  m.impl("loss_backward", &loss_backward);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -796,6 +853,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   pg.def("append", &pg_append);
   pg.def("shift_frames", &pg_shift_frames);
   pg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_graph_workspace_bytes((int)capacity); });
+  auto losses = m.def_submodule("losses", "devo_amd.losses: train.py:172-236, :254-266");
+  losses.def("forward", &loss_forward);
+  losses.def("backward", &loss_backward);
+  losses.def("state_bytes", [](int64_t Ec, int64_t n, int64_t Ef, int64_t n_patches, int64_t dtype) {
+    return (int64_t)devo_loss_state_bytes((int)Ec, (int)n, (int)Ef, (int)n_patches, (int)dtype);
+  });
   m.def("bump_version", &bump_version, "count a raw-pointer write as an in-place edit of the tensor (no launch)");
 
   auto lie = m.def_submodule("lietorch_backends", "devo/lietorch/src/lietorch.cpp:286-316 (SE3)");

@@ -69,9 +69,15 @@ class TrainNet(nn.Module):
                     raise NotImplementedError(f"randaug with norm {self.norm!r} is not implemented")
         return images
 
-    def forward(self, batch, iters=18, corr_dropout=0.2, flow_weight=0.1, pose_weight=10.0):
+    OBJECTIVES = ("bench", "reference")
+
+    def forward(self, batch, iters=18, corr_dropout=0.2, flow_weight=0.1, pose_weight=10.0, objective="bench"):
         """One sequence (batch 1) through `iters` update iterations on its patch graph -> scalar loss
-        (enet.py:300-370 on a fixed full graph + train.py:172-236)."""
+        (enet.py:300-370 on a fixed full graph + train.py:172-236).  objective: "bench", the simplified composition below (what
+        bench.py --mode train measures), or "reference", the reference's loss through devo_amd.losses (scale-aligned pose term, the
+        scorer term in the last iteration, train.py's default scores weight)."""
+        if objective not in self.OBJECTIVES:
+            raise ValueError(f"objective {objective!r}: one of {self.OBJECTIVES}")
         if "wiring_check" in batch:
             # not a training step: sum(parameters) * factor, so that a CPU / gloo run can check the DDP wiring of THIS module
             # (every parameter in the all-reduced bucket) without the HIP kernels — tests/test_distributed_gloo.py
@@ -98,6 +104,12 @@ class TrainNet(nn.Module):
         ci, cj, ck = ii[close], jj[close], kk[close]
         with torch.no_grad():
             coords_gt, valid_gt = pops.transform(Ps, b["patches_gt"], b["intr"], ci, cj, ck, valid=True)[:2]
+        if objective == "reference":
+            from . import losses
+            far = ((dij > 0) & (dij <= 16)).nonzero().squeeze(1)         # enet.py:368: the edges of the scorer term
+            fi16, fj16, fk16 = ii[far], jj[far], kk[far]
+            with torch.no_grad():
+                coords_gt_far, valid_far = pops.transform(Ps, b["patches_gt"], b["intr"], fi16, fj16, fk16, valid=True)[:2]
         fi, fj = torch.meshgrid(torch.arange(n, device=ii.device), torch.arange(n, device=ii.device), indexing="ij")
         fk = fi != fj
         fi, fj = fi[fk], fj[fk]
@@ -118,6 +130,14 @@ class TrainNet(nn.Module):
                 Gs, patches = BA(Gs, patches, b["intr"], target, weight, 1e-4, ii, jj, kk, bounds, ep=10.0, fixedp=1, n_frames=n)
             # flow loss over the close edges (train.py:177-181), pose loss over all frame pairs (:199-225, without the scale alignment)
             cf = pops.transform(Gs, patches, b["intr"], ci, cj, ck)
+            if objective == "reference":                               # enet.py:362-369 + train.py:176-236
+                scorer = None
+                if it == iters - 1:
+                    with torch.no_grad():
+                        coords_far = pops.transform(Gs, patches, b["intr"], fi16, fj16, fk16)
+                    scorer = (scores, valid_far[0], coords_far[0], coords_gt_far[0], torch.index_select(weight.detach()[0], 0, far), fk16)
+                loss = loss + losses.iteration_loss(valid_gt, cf, coords_gt, Gs, Ps, index=it, flow_weight=flow_weight, pose_weight=pose_weight, scorer=scorer)[0]
+                continue
             e = (cf - coords_gt).norm(dim=-1).reshape(-1, self.P * self.P)
             ok = valid_gt.reshape(-1) > 0.5
             flow_loss = (e.min(dim=-1).values * ok).sum() / ok.sum().clamp(min=1)
@@ -130,6 +150,8 @@ class TrainNet(nn.Module):
             loss = loss + flow_weight * flow_loss
             if it >= 2:
                 loss = loss + pose_weight * pose_loss
+        if objective == "reference":
+            return loss
         return loss + 1e-3 * scores.mean()                      # (the reference's scorer term, train.py:226-232, reduced to a mean)
 
 
@@ -172,10 +194,10 @@ def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", ra
     return net, model, opt
 
 
-def train_step(model, opt, batch, iters=18, clip=10.0):
-    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step (train.py:166-250)."""
+def train_step(model, opt, batch, iters=18, clip=10.0, objective="bench"):
+    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step (train.py:166-250).  objective: TrainNet.forward's."""
     opt.zero_grad(set_to_none=True)
-    loss = model(batch, iters=iters)
+    loss = model(batch, iters=iters, objective=objective)
     loss.backward()
     torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
     opt.step()

@@ -33,7 +33,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                               6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
                               7: devo_voxel_augment, devo_voxel_augment_workspace_bytes;
                               8: devo_voxel_resample, devo_depth_normalise, devo_depth_normalise_workspace_bytes;
-                              9: devo_graph_motion, devo_graph_keyframe, devo_graph_remove, devo_graph_append, devo_graph_shift_frames, devo_graph_workspace_bytes;
+                              9: devo_graph_motion, devo_graph_keyframe, devo_graph_remove, devo_graph_append, devo_graph_shift_frames, devo_graph_workspace_bytes
+                                 (devo_loss_state_bytes, devo_loss_forward, devo_loss_backward joined version 9: new symbols, no argument list changed);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -708,6 +709,36 @@ int devo_graph_append(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old
  * is `tensors[s]` (HOST array of device pointers), contiguous, with rows of row_bytes[s] (HOST array) bytes; rows k + 1 .. n - 1 of
  * each move down by one (row r <- row r + 1 for r = k .. n - 2, in place). */
 int devo_graph_shift_frames(void* const* tensors, const int64_t* row_bytes, int count, int k, int n, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The training loss of one update iteration (train.py:172-236 and the metrics of :254-266); T = fp32 or fp64 throughout.
+ *   flow term   x, y T [Ec, P, P, 2] (p_ij and its ground truth over the close edges), v T [Ec]: the mean over the edges with v > 0.5
+ *               of the smallest of the P x P residual norms (NaN when there is none); px1 = the share of ALL pixels below 0.25.
+ *   pose term   Gs, Ps T [n, 7], 2 <= n <= DEVO_LOSS_MAX_POSES: both inverted, the prediction's translations scaled by
+ *               s = min(Var(t2) / sum of the singular values of cov(t2, t1), 10) (kabsch_umeyama, :54-65; fp64, no reflection
+ *               correction, a constant for the adjoint), e1 = log(dP dG^-1) over the n (n - 1) ordered pairs, tr / ro = mean norms.
+ *   scorer term (scores != NULL; the last iteration) scores T [n_patches]; v_full T [Ef], x_full, y_full T [Ef, P, P, 2],
+ *               ba_weights T [Ef, 2], kk i64 [Ef]: mean over the edges with v_full >= 0.5 of (-log(mean w) / 2 + 1) * scores[kk] * min
+ *               residual + mean(-log(max(scores, 1e-6))).  deterministic != 0: the adjoint's scatter over kk in a fixed order, else atomics.
+ * loss T [1] = flow_weight * flow + scores_weight * scorer (+ pose_weight * pose when use_pose != 0).
+ * stats f32 [DEVO_LOSS_STATS] = {flow, pose, tr, ro, px1, r1, r2, t1, t2, scores, scale}.
+ * state: devo_loss_state_bytes(Ec, n, Ef, n_patches, dtype) bytes (Ef = n_patches = 0 without the scorer term), 16-byte aligned;
+ * the partial sums and the adjoints of the three terms for a unit incoming gradient.  It belongs to this call until its backward has run.
+ * Launches: forward 2 (+ 2 with the scorer term), backward 1.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_LOSS_STATS 11
+#define DEVO_LOSS_AUX 8
+#define DEVO_LOSS_MAX_POSES 128
+size_t devo_loss_state_bytes(int Ec, int n, int Ef, int n_patches, int dtype);
+int devo_loss_forward(const void* x, const void* y, const void* v, int Ec, int P, const void* Gs, const void* Ps, int n, const void* scores, int n_patches,
+                      const void* v_full, const void* x_full, const void* y_full, const void* ba_weights, const int64_t* kk, int Ef, int deterministic,
+                      double flow_weight, double pose_weight, double scores_weight, int use_pose, void* loss, float* stats, void* state, size_t state_bytes,
+                      int dtype, devo_stream_t stream);
+/* g T [1] (the gradient arriving at loss) and the state of the forward call with the same sizes and weights (pose_weight = 0 where the
+ * pose term was not weighted in) -> g_coords T [Ec, P, P, 2] (every element written), g_Gs T [n, 7] (lietorch's embedding: the tangent
+ * in the first six), g_scores T [n_patches]; each may be NULL. */
+int devo_loss_backward(const void* g, const void* state, size_t state_bytes, int Ec, int P, int n, int Ef, int n_patches, double flow_weight, double pose_weight,
+                       double scores_weight, void* g_coords, void* g_Gs, void* g_scores, int dtype, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
