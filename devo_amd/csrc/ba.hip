@@ -1,10 +1,10 @@
-// fastba for gfx950: sparse Gauss-Newton bundle adjustment (inference variant), reprojection, transform
-// and the temporal-neighbour graph helper.  Replaces devo/fastba/ba_cuda.cu + ba.cpp (module cuda_ba,
-// ba.cpp:152-157) and fuses devo/projective_ops.py:53-105.
+// fastba for gfx950: sparse Gauss-Newton bundle adjustment (inference variant) and the differentiable Gauss-Newton step of training.
+// Replaces devo/fastba/ba_cuda.cu + ba.cpp (module cuda_ba, ba.cpp:152-157); the graph index tables are ba_tables.hip's, the fused
+// reprojection (devo/projective_ops.py:53-105) transform.hip's.
 //
 // Design.  The reference accumulates the normal equations with 340 global float
 // atomics per edge onto a few thousand addresses, then runs ~20 ATen launches + cuSOLVER (host sync) per
-// Gauss-Newton iteration.  Here the edge list is grouped by patch once per call (integer counting sort,
+// Gauss-Newton iteration.  Here the edge list is grouped by patch once per call (ba_tables.hip: integer counting sort,
 // bit-exact `unique`), and each iteration is four launches with no host synchronisation:
 //   ba_accumulate : one WAVE per patch.  Lanes = the patch's edges.  Per-patch quantities (C, u, the
 //                   source-frame E block, B_ii, v_i) are reduced with wavefront shuffles; the patch's
@@ -15,7 +15,7 @@
 //   ba_solve      : one workgroup, LDS-resident blocked (6x6) Cholesky with the right-hand side carried as
 //                   an extra row, blocked back-substitution.
 //   ba_retract    : pose retraction Exp(dX) * G and per-patch depth update  dz = Q (u - e^T dX).
-#include "common.h"
+#include "ba_layout.h"
 #include <cstddef>
 #include "se3_dev.h"
 #include "corr_tile.h"
@@ -25,15 +25,8 @@
 
 namespace devo {
 
-constexpr int BA_MAXN_LDS = 32;      // optimised poses per call whose system (6N <= 192 rows) lives in LDS
-constexpr int BA_MAXN = 128;         // beyond BA_MAXN_LDS: the system stays in global memory (device atomics, k_ba_solve_t<true>); the limit is
-                                     // the solver's LDS tables (factored diagonal blocks + inverses) and ba_sig's 8 bits for N
 constexpr int ACC_WAVES = 8;         // waves per ba_accumulate workgroup
 constexpr int ACC_THREADS = ACC_WAVES * 64;
-constexpr int ACC_MAX_WG = 256;      // partial systems written per iteration
-
-struct BaMeta { int n_seg; int fail; int sig; int pad; };   // sig: what the workspace was prepared for (ba_sig)
-__host__ __device__ __forceinline__ int ba_sig(int E, int N) { return (int)(0x5ec0de00u ^ ((unsigned)E * 2654435761u) ^ ((unsigned)N << 24)); }
 
 // ------------------------------------------------------------------------------------------------- utilities
 // Sum over the 64 lanes, returned to every lane.  Round 6: DPP adds on the vector ALU — the scan of corr_tile.h's wave_inclusive_sum (row_shr
@@ -66,528 +59,6 @@ __device__ __forceinline__ int ftab_lookup(int my_le, int f) { return __shfl(my_
 __device__ __forceinline__ void wave_lds_sync() {
   __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
   __builtin_amdgcn_wave_barrier();
-}
-
-// In-place exclusive scan of data[0..n) by ONE workgroup of 1024 threads; data[n] = total (returned to all).  s_part: >= 48 ints.
-// Round 6: every wave owns a contiguous span and walks it 64 consecutive elements at a time — coalesced loads, four steps in flight, a DPP scan per
-// step, the carry in a scalar — where rounds 1-5 gave every THREAD a contiguous chunk and waited for each of its loads in turn: 191 us for the 131 072
-// hash slots of cuda_ba.neighbors at DEVO's steady-state size (45 312 edges), ~0.75 us per element and thread.  Integer sums: any order, the same bits.
-__device__ __forceinline__ int block_excl_scan_1024(int* data, int n, int* s_part) {
-  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-  const int span = ((n + 16 * 64 - 1) / (16 * 64)) * 64;     // elements per wave, whole steps of 64
-  const int lo = min(n, wave * span), hi = min(n, lo + span);
-  constexpr int UB = 4;
-  int s = 0;
-  for (int i0 = lo; i0 < hi; i0 += 64 * UB) {
-    int v[UB];
-#pragma unroll
-    for (int u = 0; u < UB; u++) { const int i = i0 + 64 * u + lane; v[u] = (i < hi) ? data[i] : 0; }
-#pragma unroll
-    for (int u = 0; u < UB; u++) s += v[u];
-  }
-  const int x = wave_inclusive_sum(s);
-  if (lane == 63) s_part[wave] = x;              // the wave's total
-  __syncthreads();
-  if (wave == 0) {
-    const int w = (lane < 16) ? s_part[lane] : 0;
-    int y = w;
-#pragma unroll
-    for (int off = 1; off < 16; off <<= 1) { const int v = __shfl_up(y, off); if (lane >= off) y += v; }
-    if (lane < 16) s_part[16 + lane] = y - w;   // exclusive prefix of every wave
-    if (lane == 15) s_part[32] = y;             // grand total
-  }
-  __syncthreads();
-  int carry = s_part[16 + wave];                 // (wave-uniform)
-  for (int i0 = lo; i0 < hi; i0 += 64 * UB) {
-    int v[UB];
-#pragma unroll
-    for (int u = 0; u < UB; u++) { const int i = i0 + 64 * u + lane; v[u] = (i < hi) ? data[i] : 0; }
-#pragma unroll
-    for (int u = 0; u < UB; u++) {
-      const int i = i0 + 64 * u + lane;
-      const int inc = wave_inclusive_sum(v[u]);
-      if (i < hi) data[i] = carry + inc - v[u];
-      carry += __builtin_amdgcn_readlane(inc, 63);
-    }
-  }
-  const int total = s_part[32];
-  if (t == 1023) data[n] = total;
-  __syncthreads();
-  return total;
-}
-__global__ __launch_bounds__(1024) void k_excl_scan(int* data, int n, int* total_out) {
-  __shared__ int s_part[1024];
-  const int total = block_excl_scan_1024(data, n, s_part);
-  if (threadIdx.x == 0 && total_out) *total_out = total;
-}
-
-// ---- the multi-kernel preparation works on the RANGE of patch ids the edge list holds, not on all patch slots (round 6): DEVO's buffers have
-// 2048 frames x 96 = 196 608 slots, a sliding-window graph touches the 2 112 patches of 22 frames — flags, scan and the unique-id sweep over the
-// slots cost 380 us there, over the range 30.  range[0] = max(-k), range[1] = max(k) over the valid ids (both start at 0x80808080: "minus infinity").
-__device__ __forceinline__ void kk_range_body(const int64_t* __restrict__ kk, int E, int Np, int* __restrict__ range) {
-  int nlo = (int)0x80808080, hi = (int)0x80808080;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int64_t k = kk[e];
-    if (k >= 0 && k < Np) { nlo = max(nlo, -(int)k); hi = max(hi, (int)k); }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) { nlo = max(nlo, __shfl_xor(nlo, o)); hi = max(hi, __shfl_xor(hi, o)); }
-  __shared__ int s_r[2][4];                                    // one pair of atomics per workgroup: they all hit one cache line
-  if ((threadIdx.x & 63) == 0) { s_r[0][threadIdx.x >> 6] = nlo; s_r[1][threadIdx.x >> 6] = hi; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const int a = max(max(s_r[0][0], s_r[0][1]), max(s_r[0][2], s_r[0][3])), b = max(max(s_r[1][0], s_r[1][1]), max(s_r[1][2], s_r[1][3]));
-    if (b != (int)0x80808080) { atomicMax(&range[0], a); atomicMax(&range[1], b); }
-  }
-}
-__global__ void k_kk_range(const int64_t* __restrict__ kk, int E, int Np, int* __restrict__ range) { kk_range_body(kk, E, Np, range); }
-__device__ __forceinline__ void kk_range(const int* __restrict__ range, int& kmin, int& Rg) {
-  const int nlo = range[0], hi = range[1];
-  const bool any = hi != (int)0x80808080;
-  kmin = any ? -nlo : 0;
-  Rg = any ? hi - kmin + 1 : 0;
-}
-__device__ __forceinline__ void flag_ids_r_body(const int64_t* __restrict__ kk, int E, int Np, int* flags, const int* __restrict__ range) {
-  int kmin, Rg;
-  kk_range(range, kmin, Rg);
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int64_t k = kk[e];
-    if (k >= 0 && k < Np) flags[(int)k - kmin] = 1;
-  }
-}
-__global__ void k_flag_ids_r(const int64_t* __restrict__ kk, int E, int Np, int* flags, const int* __restrict__ range) { flag_ids_r_body(kk, E, Np, flags, range); }
-// k_excl_scan over a length read on the device: mode 0 = the id range (range), mode 1 = min(*n_ptr, cap) (the segment counts: n_seg of them)
-__device__ __forceinline__ void excl_scan_dev_body(int* data, const int* __restrict__ n_ptr, int mode, int cap, int* total_out) {
-  __shared__ int s_part[1024];
-  int n;
-  if (mode == 0) { int kmin; kk_range(n_ptr, kmin, n); } else n = min(*n_ptr, cap);
-  const int total = block_excl_scan_1024(data, n, s_part);
-  if (threadIdx.x == 0 && total_out) *total_out = total;
-  if (mode == 1) for (int i = n + 1 + threadIdx.x; i <= cap; i += 1024) data[i] = total;     // segment starts beyond n_seg = E: any reader sees empty tails
-}
-__global__ __launch_bounds__(1024) void k_excl_scan_dev(int* data, const int* __restrict__ n_ptr, int mode, int cap, int* total_out) { excl_scan_dev_body(data, n_ptr, mode, cap, total_out); }
-// Few, large segments (the Update operator's frame-pair groups: 45 312 edges in 210 groups) make the per-edge device atomics of the counting and
-// scattering passes queue on a handful of addresses (23 us each where the patch groups take 5): when n_seg <= SEG_LDS_MAX and the average segment
-// holds >= 64 edges, every workgroup counts in LDS first and issues ONE device atomic per segment it met.
-constexpr int SEG_LDS_MAX = 1024;
-__device__ __forceinline__ bool seg_lds_path(int n_seg, int E) { return n_seg <= SEG_LDS_MAX && (long long)n_seg * 64 <= E; }
-__device__ __forceinline__ void rank_edges_r_body(const int64_t* __restrict__ kk, int E, int Np, const int* __restrict__ rank, int* ku, int* kx,
-                                                      int* counts, const int* __restrict__ range, const int* __restrict__ n_seg_p) {
-  __shared__ int s_hist[SEG_LDS_MAX];
-  int kmin, Rg;
-  kk_range(range, kmin, Rg);
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x, gsz = blockDim.x * gridDim.x;
-  const int n_seg = max(*n_seg_p, 1);                         // (edges with bad ids count for segment 0, even when no id is good)
-  if (seg_lds_path(n_seg, E)) {
-    for (int b = threadIdx.x; b < n_seg; b += blockDim.x) s_hist[b] = 0;
-    __syncthreads();
-    for (int e = gid; e < E; e += gsz) {
-      const int64_t k = kk[e];
-      const int r = (k >= 0 && k < Np) ? rank[(int)k - kmin] : 0;
-      ku[e] = r;
-      atomicAdd(&s_hist[r], 1);
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < n_seg; b += blockDim.x) { const int c = s_hist[b]; if (c) atomicAdd(&counts[b], c); }
-  } else {
-    for (int e = gid; e < E; e += gsz) {
-      const int64_t k = kk[e];
-      const int r = (k >= 0 && k < Np) ? rank[(int)k - kmin] : 0;
-      ku[e] = r;
-      atomicAdd(&counts[r], 1);
-    }
-  }
-  for (int p = gid; p < Rg; p += gsz)
-    if (rank[p + 1] != rank[p]) kx[rank[p]] = kmin + p;
-}
-__global__ __launch_bounds__(256) void k_rank_edges_r(const int64_t* __restrict__ kk, int E, int Np, const int* __restrict__ rank, int* ku, int* kx,
-                                                      int* counts, const int* __restrict__ range, const int* __restrict__ n_seg_p) { rank_edges_r_body(kk, E, Np, rank, ku, kx, counts, range, n_seg_p); }
-
-__global__ void k_flag_ids(const int64_t* __restrict__ kk, int E, int Np, int* flags) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    int64_t k = kk[e];
-    if (k >= 0 && k < Np) flags[k] = 1;
-  }
-}
-// rank[] = exclusive scan of flags (flags[] consumed).  ku = rank of the edge's patch, kx = sorted unique ids.
-__global__ void k_rank_edges(const int64_t* __restrict__ kk, int E, int Np, const int* __restrict__ rank,
-                             int* ku, int* kx, int* counts) {
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x, gsz = blockDim.x * gridDim.x;
-  for (int e = gid; e < E; e += gsz) {
-    int64_t k = kk[e];
-    int r = (k >= 0 && k < Np) ? rank[k] : 0;
-    ku[e] = r;
-    atomicAdd(&counts[r], 1);
-  }
-  for (int p = gid; p < Np; p += gsz)
-    if (rank[p + 1] != rank[p]) kx[rank[p]] = p;
-}
-__global__ void k_scatter_edges(const int* __restrict__ ku, int E, const int* __restrict__ seg_start, int* cursor, int* perm) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    int s = ku[e];
-    perm[seg_start[s] + atomicAdd(&cursor[s], 1)] = e;
-  }
-}
-// The same with the workgroup's edges ranked in LDS first (see seg_lds_path): one device atomic per (workgroup, segment) reserves the slots.
-__device__ __forceinline__ void scatter_edges_seg_body(const int* __restrict__ ku, int E, const int* __restrict__ seg_start, int* cursor, int* perm,
-                                                           const int* __restrict__ n_seg_p) {
-  __shared__ int s_hist[SEG_LDS_MAX];
-  const int n_seg = max(*n_seg_p, 1);
-  const int gsz = blockDim.x * gridDim.x;
-  if (!seg_lds_path(n_seg, E)) {
-    for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += gsz) {
-      const int s = ku[e];
-      perm[seg_start[s] + atomicAdd(&cursor[s], 1)] = e;
-    }
-    return;
-  }
-  for (int base = blockIdx.x * blockDim.x; base < E; base += gsz) {          // (uniform per workgroup: the barriers below are safe)
-    for (int b = threadIdx.x; b < n_seg; b += blockDim.x) s_hist[b] = 0;
-    __syncthreads();
-    const int e = base + threadIdx.x;
-    int s = 0, lr = 0;
-    if (e < E) { s = ku[e]; lr = atomicAdd(&s_hist[s], 1); }
-    __syncthreads();
-    for (int b = threadIdx.x; b < n_seg; b += blockDim.x) { const int c = s_hist[b]; if (c) s_hist[b] = atomicAdd(&cursor[b], c); }
-    __syncthreads();
-    if (e < E) perm[seg_start[s] + s_hist[s] + lr] = e;
-    __syncthreads();
-  }
-}
-__global__ __launch_bounds__(256) void k_scatter_edges_seg(const int* __restrict__ ku, int E, const int* __restrict__ seg_start, int* cursor, int* perm,
-                                                           const int* __restrict__ n_seg_p) { scatter_edges_seg_body(ku, E, seg_start, cursor, perm, n_seg_p); }
-// Restore a deterministic (ascending edge id) order inside every segment: rank sort, one wave per segment.
-__device__ __forceinline__ void sort_segments_body(const int* __restrict__ seg_start, BaMeta* __restrict__ meta, int sig, const int* __restrict__ in, int* out) {
-  const int* n_seg_p = &meta->n_seg;
-  if (blockIdx.x == 0 && threadIdx.x == 0) meta->sig = sig;      // the workspace now holds a prepared graph
-  if (meta->pad) return;                                         // the list was already grouped: perm is the identity
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (blockDim.x * gridDim.x) >> 6;
-  const int n_seg = *n_seg_p;
-  for (int s = wave; s < n_seg; s += nwaves) {
-    const int a = seg_start[s], m = seg_start[s + 1] - a;
-    for (int i = lane; i < m; i += 64) {
-      int x = in[a + i], r = 0;
-      for (int j = 0; j < m; j++) r += (in[a + j] < x);
-      out[a + r] = x;
-    }
-  }
-}
-__global__ void k_sort_segments(const int* __restrict__ seg_start, BaMeta* __restrict__ meta, int sig, const int* __restrict__ in, int* out) { sort_segments_body(seg_start, meta, sig, in, out); }
-
-// ---- the multi-kernel preparation of TWO edge lists of one length in the same launches (devo_upd_graph_tables: the edges grouped by patch and by
-// frame pair, once per frame in DEVO's steady state): blockIdx.y picks the problem, every stage is one launch instead of two — 11 launches for
-// what took 22 (each ~4.5 us of a nearly idle chip).
-struct Prep2 {
-  const int64_t* kk[2]; BaMeta* meta[2]; int* rank[2]; int* counts[2]; int* cursor[2]; int* ku[2]; int* kx[2]; int* perm_a[2]; int* perm_b[2]; int* range[2];
-};
-__global__ void k_kk_range2(Prep2 p, int E, int Np) { const int y = blockIdx.y; kk_range_body(p.kk[y], E, Np, p.range[y]); }
-__global__ void k_flag_ids_r2(Prep2 p, int E, int Np) { const int y = blockIdx.y; flag_ids_r_body(p.kk[y], E, Np, p.rank[y], p.range[y]); }
-__global__ __launch_bounds__(1024) void k_excl_scan_dev2(Prep2 p, int mode, int cap) {
-  const int y = blockIdx.y;
-  if (mode == 0) excl_scan_dev_body(p.rank[y], p.range[y], 0, 0, &p.meta[y]->n_seg);
-  else excl_scan_dev_body(p.counts[y], &p.meta[y]->n_seg, 1, cap, nullptr);
-}
-__global__ __launch_bounds__(256) void k_rank_edges_r2(Prep2 p, int E, int Np) {
-  const int y = blockIdx.y;
-  rank_edges_r_body(p.kk[y], E, Np, p.rank[y], p.ku[y], p.kx[y], p.counts[y], p.range[y], &p.meta[y]->n_seg);
-}
-__global__ __launch_bounds__(256) void k_scatter_edges_seg2(Prep2 p, int E) {
-  const int y = blockIdx.y;
-  scatter_edges_seg_body(p.ku[y], E, p.counts[y], p.cursor[y], p.perm_a[y], &p.meta[y]->n_seg);
-}
-__global__ void k_sort_segments2(Prep2 p, int sig) { const int y = blockIdx.y; sort_segments_body(p.counts[y], p.meta[y], sig, p.perm_a[y], p.perm_b[y]); }
-// what the two hipMemsetAsync pairs of two preparations and the pair key's range fill did: the heads of both workspaces (meta | rank | counts | cursor)
-// to zero, the three id ranges to "minus infinity" (0x80808080)
-__global__ __launch_bounds__(256) void k_prep_clear2(int4* __restrict__ a0, int4* __restrict__ a1, long long n4, int* r0, int* r1, int* r2) {
-  const long long gid = (long long)blockIdx.x * blockDim.x + threadIdx.x, gsz = (long long)blockDim.x * gridDim.x;
-  const int4 z = make_int4(0, 0, 0, 0);
-  for (long long i = gid; i < n4; i += gsz) { a0[i] = z; a1[i] = z; }
-  if (gid < 4) { r0[gid] = (int)0x80808080; r1[gid] = (int)0x80808080; r2[gid] = (int)0x80808080; }
-}
-
-// Whole graph preparation in ONE launch (one workgroup of 1024 threads) for E <= 2^17:
-//   range of kk -> presence flags over [kmin, kmax] -> rank (sorted unique patch ids, ba_cuda.cu:435-437)
-//   -> per-patch edge counts -> segment starts -> scatter.   (k_sort_segments then fixes the in-segment order.)
-// Everything a lane needs a RETURNED atomic for lives in LDS when it fits (<= 16384 ids in range, <= 8192 unique
-// patches — DEVO's sliding window is ~2k patches); otherwise the same arrays in the workspace are used.
-constexpr int PREP_FLAGS_LDS = 16384;
-constexpr int PREP_SEGS_LDS = 8192;
-template <int CACHE>      // CACHE = 0: kk is re-read by every pass; else ceil(E / 1024) <= CACHE edges per thread in registers
-__device__ __forceinline__ void ba_prepare_body(const int64_t* __restrict__ kk, int E, int Np, int max_seg, BaMeta* meta,
-                                                int* g_rank, int* g_counts, int* g_cursor, int* ku, int* kx, int* perm_a,
-                                                int* perm_b, int sig) {
-  extern __shared__ int s_mem[];
-  int* s_part = s_mem;                       // 1024
-  int* s_flags = s_part + 1024;              // PREP_FLAGS_LDS + 1
-  int* s_counts = s_flags + PREP_FLAGS_LDS + 1;   // PREP_SEGS_LDS + 1
-  int* s_cursor = s_counts + PREP_SEGS_LDS + 1;   // PREP_SEGS_LDS
-  __shared__ int s_min, s_max;
-  const int t = threadIdx.x;
-  if (t == 0) { s_min = 0x7fffffff; s_max = -1; }
-  // patch id of edge t + 1024 i (or -1: out of range / no edge).  CACHED: all loads in flight at once, every later
-  // pass runs from registers; otherwise kk is re-read by every pass.
-  constexpr bool CACHED = CACHE > 0;
-  int kreg[CACHED ? CACHE : 1];
-  auto patch_of = [&](int i) -> int {
-    if (CACHED) return kreg[i];
-    const int e = t + 1024 * i;
-    if (e >= E) return -1;
-    const int64_t k = kk[e];
-    return (k >= 0 && k < Np) ? (int)k : -1;
-  };
-  const int iters = CACHED ? CACHE : (E + 1023) / 1024;
-  if (CACHED) {
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int e = t + 1024 * i;
-      int64_t k = -1;
-      if (e < E) k = kk[e];
-      kreg[i] = (k >= 0 && k < Np) ? (int)k : -1;
-    }
-  }
-  // Already grouped?  If the patch ids are ascending along the edge list (kk-major graphs: enet.py:300-301, any list
-  // built patch by patch) every segment is a run, the permutation is the identity and the whole counting sort below
-  // can be skipped.  headmask bit i = edge t + 1024 i starts a run.
-  __shared__ int s_last[16][CACHED ? CACHE : 1];
-  unsigned long long headmask = 0ull;                           // (up to 64 edges per thread)
-  int ascending = 0;
-  if (CACHED) {
-    const int lane_ = t & 63, wave_ = t >> 6;
-    if (lane_ == 63) {
-#pragma unroll
-      for (int i = 0; i < (CACHED ? CACHE : 1); i++) s_last[wave_][i] = kreg[i];
-    }
-    __syncthreads();
-    bool ok = true;
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int e = t + 1024 * i;
-      int prev = __builtin_amdgcn_update_dpp(0, kreg[i], 0x138, 0xf, 0xf, false);   // wave_shr:1 (lane 0 replaced below)
-      if (lane_ == 0) prev = (wave_ > 0) ? s_last[wave_ - 1][i] : (i > 0 ? s_last[15][i > 0 ? i - 1 : 0] : -1);
-      if (e < E) {
-        ok = ok && kreg[i] >= 0 && (e == 0 || prev <= kreg[i]);
-        if (e == 0 || prev != kreg[i]) headmask |= 1ull << i;
-      }
-    }
-    ascending = __syncthreads_and(ok ? 1 : 0);
-  } else {
-    __syncthreads();
-  }
-  if (CACHED && ascending) {
-    // Segment starts = the run heads, permutation = identity (ascending edge ids inside every patch by construction), and
-    // the segment of a head = the number of heads before it: heads per 64-edge chunk (chunk c = 16 i + wave covers edges
-    // 64 c .. 64 c + 63) by ballot, one wave scans the <= 512 chunk counts, no flag array / id range needed.
-    const int lane_ = t & 63, wave_ = t >> 6;
-    constexpr int NCH = 16 * (CACHED ? CACHE : 1);
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const unsigned long long hb = __ballot((headmask >> i) & 1ull);
-      if (lane_ == 0) s_part[16 * i + wave_] = __popcll(hb);
-    }
-    __syncthreads();
-    // (the first NCH / 64 waves scan 64 chunk counts each; their totals are combined by every reader)
-    constexpr int NW = NCH / 64;
-    const int v = (wave_ < NW) ? s_part[t] : 0;
-    const int x = wave_inclusive_sum(v);
-    if (wave_ < NW && lane_ == 63) s_part[NCH + wave_] = x;
-    __syncthreads();
-    int carry = 0, n_seg = 0;
-#pragma unroll
-    for (int w = 0; w < NW; w++) { const int tot = s_part[NCH + w]; if (w < wave_) carry += tot; n_seg += tot; }
-    if (wave_ < NW) s_part[t] = carry + x - v;
-    __syncthreads();
-    if (t == 0) { meta->n_seg = n_seg; meta->fail = 0; meta->pad = 1; meta->sig = sig; }
-    int cbase[CACHED ? CACHE : 1];                         // all chunk bases in flight at once, ahead of the divergent stores
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) cbase[i] = s_part[16 * i + wave_];
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int e = t + 1024 * i;
-      const bool head = (headmask >> i) & 1ull;
-      const unsigned long long hb = __ballot(head);
-      if (e < E) {
-        perm_b[e] = e;
-        if (head) { const int r = cbase[i] + __popcll(hb & ((1ull << lane_) - 1ull)); g_counts[r] = e; kx[r] = kreg[i]; }
-      }
-    }
-    for (int i = n_seg + t; i <= max_seg; i += 1024) g_counts[i] = E;      // segment n_seg starts at E; empty tails
-    return;
-  }
-  int lo = 0x7fffffff, hi = -1;
-#pragma unroll
-  for (int i = 0; i < iters; i++) { const int k = patch_of(i); if (k >= 0) { lo = min(lo, k); hi = max(hi, k); } }
-  for (int off = 32; off >= 1; off >>= 1) { lo = min(lo, __shfl_xor(lo, off)); hi = max(hi, __shfl_xor(hi, off)); }
-  if ((t & 63) == 0) { atomicMin(&s_min, lo); atomicMax(&s_max, hi); }
-  __syncthreads();
-  const int kmin = s_min, kmax = s_max;
-  const int Rg = (kmax >= kmin) ? kmax - kmin + 1 : 0;
-  int* rank = (Rg <= PREP_FLAGS_LDS) ? s_flags : g_rank;
-  for (int i = t; i <= Rg; i += 1024) rank[i] = 0;
-  __syncthreads();
-#pragma unroll
-  for (int i = 0; i < iters; i++) { const int k = patch_of(i); if (k >= 0) rank[k - kmin] = 1; }
-  __syncthreads();
-  const int n_seg = block_excl_scan_1024(rank, Rg, s_part);
-  // (sig: the workspace holds a prepared graph once this kernel is through — the in-segment order is restored below)
-  if (t == 0) { meta->n_seg = n_seg; meta->fail = 0; meta->pad = ascending; meta->sig = sig; }
-  int* counts = (n_seg <= PREP_SEGS_LDS) ? s_counts : g_counts;
-  int* cursor = (n_seg <= PREP_SEGS_LDS) ? s_cursor : g_cursor;
-  for (int i = t; i <= n_seg; i += 1024) counts[i] = 0;
-  for (int i = t; i < n_seg; i += 1024) cursor[i] = 0;
-  __syncthreads();
-  // Runs of consecutive lanes with the same segment (the edges of a patch are usually adjacent in the edge list) share
-  // ONE LDS atomic issued by the first lane of the run — same-address LDS atomics serialise, and this workgroup is the
-  // only one running.  (All lanes execute the ballots / shuffles; only the stores are guarded.)
-  const int lane = t & 63;
-  auto run_of = [&](int key, int& head_lane, int& next_head) {
-    const int prev = __shfl_up(key, 1);
-    const bool head = (lane == 0) || (prev != key);
-    const unsigned long long H = __ballot(head);
-    const unsigned long long upto = (2ULL << lane) - 1ULL;            // bits 0..lane (all ones for lane 63)
-    head_lane = 63 - __clzll((long long)(H & upto));
-    const unsigned long long above = H & ~upto;
-    next_head = above ? __ffsll((long long)above) - 1 : 64;
-  };
-  // segment of every edge (edges with a bad patch id go to segment 0, like before).  CACHED: the run head's atomic
-  // RETURNS the run's offset inside its segment, so every edge knows its place before the segment starts exist and the
-  // scatter pass needs no second round of atomics.
-  int posin[CACHED ? CACHE : 1];
-  if (CACHED) {
-    // three batched sweeps (LDS reads / shuffles / atomics are each issued back to back for all of a thread's edges —
-    // interleaved per edge, every returned LDS atomic would serialise the whole dependent chain behind it)
-    // (one packed register per edge besides its segment: 1024 threads leave 128 VGPRs per thread)
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int k = kreg[i];
-      kreg[i] = (t + 1024 * i < E) ? ((k >= 0) ? rank[k - kmin] : 0) : -1;
-    }
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      int hl, nh;
-      run_of(kreg[i], hl, nh);
-      posin[i] = hl | (nh << 8);                               // head lane of my run | lane after its end
-    }
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int hl = posin[i] & 255, nh = posin[i] >> 8;
-      int base = 0;
-      if (kreg[i] >= 0 && hl == lane) base = atomicAdd(&counts[kreg[i]], nh - lane);   // E < 2^25: fits next to hl
-      posin[i] = (base << 6) | hl;
-    }
-#pragma unroll
-    for (int i = 0; i < (CACHED ? CACHE : 1); i++) {
-      const int hl = posin[i] & 63;
-      posin[i] = __shfl(posin[i] >> 6, hl) + (lane - hl);
-    }
-  } else {
-    for (int i = 0; i < iters; i++) {
-      const int e = t + 1024 * i;
-      int r = -1;
-      if (e < E) { const int k = patch_of(i); r = (k >= 0) ? rank[k - kmin] : 0; ku[e] = r; }   // ku: re-read by the scatter pass
-      int hl, nh;
-      run_of(r, hl, nh);
-      if (r >= 0 && hl == lane) atomicAdd(&counts[r], nh - lane);
-    }
-  }
-  for (int p = t; p < Rg; p += 1024)
-    if (rank[p + 1] != rank[p]) kx[rank[p]] = kmin + p;
-  __syncthreads();
-  block_excl_scan_1024(counts, n_seg, s_part);
-#pragma unroll
-  for (int i = 0; i < iters; i++) {
-    const int e = t + 1024 * i;
-    if (CACHED) {
-      const int sgm = kreg[i];
-      if (sgm >= 0) perm_a[counts[sgm] + posin[i]] = e;
-    } else {
-      const int sgm = e < E ? ku[e] : -1;
-      int hl, nh;
-      run_of(sgm, hl, nh);
-      int base = 0;
-      if (sgm >= 0 && hl == lane) base = atomicAdd(&cursor[sgm], nh - lane);
-      base = __shfl(base, hl);
-      if (sgm >= 0) perm_a[counts[sgm] + base + (lane - hl)] = e;
-    }
-  }
-  // publish the segment starts: entries beyond n_seg = E so that any reader sees empty tails
-  for (int i = t; i <= max_seg; i += 1024) g_counts[i] = (i <= n_seg) ? counts[i] : E;
-  // restore a deterministic (ascending edge id) order inside every segment: rank sort, one wave per segment (the work of
-  // k_sort_segments, which the multi-kernel path for huge edge lists still launches)
-  __threadfence_block();
-  __syncthreads();
-  // round 6: two segments per pass, one per half of the wave, the ranks from v_readlane instead of one (L1-hit) load per comparison, the next
-  // pass's elements requested before this pass's ranks are counted — DEVO's steady-state graph (45 312 edges in devo.py's order, 2 112 patches of
-  // ~21 edges) spent 260 of this kernel's 280 us in the loop below when every comparison was a load
-  {
-    const int wv16 = t >> 6, half = lane >> 5, l = lane & 31;
-    auto fetch = [&](int pair, int& a, int& m, int& x) {
-      const int sg = 2 * pair + half;
-      a = 0; m = 0;
-      if (sg < n_seg) { a = counts[sg]; m = counts[sg + 1] - a; }
-      x = (l < m && m <= 32) ? perm_a[a + l] : 0x7fffffff;
-    };
-    const int npair = (n_seg + 1) >> 1;
-    constexpr int SD = 6;                                        // passes whose elements are in flight together (one round trip per SD passes)
-    for (int base = wv16; base < npair; base += 16 * SD) {
-      int a[SD], m[SD], x[SD];
-#pragma unroll
-      for (int u = 0; u < SD; u++) {
-        a[u] = 0; m[u] = 0; x[u] = 0x7fffffff;
-        if (base + 16 * u < npair) fetch(base + 16 * u, a[u], m[u], x[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < SD; u++) {
-        const int pair = base + 16 * u;
-        if (pair >= npair) break;                                  // (wave-uniform)
-        const int mmax = max(__builtin_amdgcn_readlane(m[u], 0), __builtin_amdgcn_readlane(m[u], 32));
-        if (mmax <= 32) {
-          int r = 0;
-          for (int j = 0; j < mmax; j++) {
-            const int xa = __builtin_amdgcn_readlane(x[u], j), xb = __builtin_amdgcn_readlane(x[u], 32 + j);     // (j is wave-uniform)
-            r += ((half ? xb : xa) < x[u]) ? 1 : 0;
-          }
-          if (l < m[u]) perm_b[a[u] + r] = x[u];
-        } else {
-          // a long segment in the pair: the general loop for both (rare: a patch with more than 32 edges)
-          for (int h = 0; h < 2; h++) {
-            const int sg = 2 * pair + h;
-            if (sg >= n_seg) break;
-            const int a2 = counts[sg], m2 = counts[sg + 1] - a2;
-            for (int i = lane; i < m2; i += 64) {
-              const int x2 = perm_a[a2 + i];
-              int r = 0;
-              for (int jq = 0; jq < m2; jq++) r += (perm_a[a2 + jq] < x2);
-              perm_b[a2 + r] = x2;
-            }
-          }
-        }
-      }
-    }
-  }
-}
-
-template <int CACHE>
-__global__ __launch_bounds__(1024) void k_ba_prepare(const int64_t* __restrict__ kk, int E, int Np, int max_seg, BaMeta* meta,
-                                                     int* g_rank, int* g_counts, int* g_cursor, int* ku, int* kx, int* perm_a,
-                                                     int* perm_b, int sig) {
-  ba_prepare_body<CACHE>(kk, E, Np, max_seg, meta, g_rank, g_counts, g_cursor, ku, kx, perm_a, perm_b, sig);
-}
-
-template <int CACHE>
-__global__ __launch_bounds__(ORDER_THREADS) void k_order_only(const int* __restrict__ bins, int BE, int nbins, int* __restrict__ order, int starts) {
-  corr_order_body<CACHE>(bins, BE, nbins, order, (int)blockIdx.x, (int)gridDim.x, starts != 0);
-}
-
-// Workgroup 0: the BA's index preparation; workgroups 1 .. G: the ordering step of the lookup's locality plan (corr_plan.h).
-// Latency-bound kernels that do not depend on each other run side by side in one launch.
-template <int CACHE>
-__global__ __launch_bounds__(1024) void k_prepare_and_order(const int64_t* __restrict__ kk, int E, int Np, int max_seg, BaMeta* meta,
-                                                            int* g_rank, int* g_counts, int* g_cursor, int* ku, int* kx, int* perm_a,
-                                                            int* perm_b, int sig, const int* __restrict__ bins, int nbins, int* __restrict__ order,
-                                                            int starts) {
-  if (blockIdx.x == 0) ba_prepare_body<CACHE>(kk, E, Np, max_seg, meta, g_rank, g_counts, g_cursor, ku, kx, perm_a, perm_b, sig);
-  else corr_order_body<CACHE>(bins, E, nbins, order, (int)blockIdx.x - 1, (int)gridDim.x - 1, starts != 0);
 }
 
 // ------------------------------------------------------------------------------------------------- per-edge maths
@@ -1237,7 +708,6 @@ constexpr auto k_ba_accumulate = k_ba_accumulate_t<false>;
 // Workgroup = one 32 x 32 tile of the lower triangle x one chunk of 128 patches; 2 x 2 outputs per thread; float atomics into S
 // (1 344 workgroups x 1 024 outputs at the stress size) — or, when the launcher has scratch for it (the partial systems' area is free
 // by then), one partial tile per workgroup that k_ba_damp adds in a fixed order: bit-reproducible results.
-constexpr int SCH_T = 32, SCH_K = 128;
 __global__ __launch_bounds__(256) void k_ba_schur(const float* __restrict__ patch_rec, const float* __restrict__ patch_col,
                                                   const BaMeta* __restrict__ meta, int N, int max_seg, float* __restrict__ S,
                                                   float* __restrict__ part) {
@@ -2159,330 +1629,7 @@ __global__ void k_bt_edge(const float* __restrict__ terms, const int64_t* __rest
   }
 }
 
-// ------------------------------------------------------------------------------------------------- reproject / transform
-__global__ void k_reproject(const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ intr,
-                            const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const int64_t* __restrict__ kk,
-                            float* __restrict__ coords, int E, int P) {
-  const float fx = intr[0], fy = intr[1], cx = intr[2], cy = intr[3];
-  const int PPx = P * P;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const float* pi = poses + ii[e] * 7;
-    const float* pj = poses + jj[e] * 7;
-    float ti[3] = {pi[0], pi[1], pi[2]}, qi[4] = {pi[3], pi[4], pi[5], pi[6]};
-    float tj[3] = {pj[0], pj[1], pj[2]}, qj[4] = {pj[3], pj[4], pj[5], pj[6]};
-    float tij[3], qij[4];
-    fb_relSE3(ti, qi, tj, qj, tij, qij);
-    const float* pk = patches + kk[e] * 3 * PPx;
-    float* out = coords + (int64_t)e * 2 * PPx;
-    for (int i = 0; i < PPx; i++) {
-      float Xi[4] = {(pk[i] - cx) / fx, (pk[PPx + i] - cy) / fy, 1.0f, pk[2 * PPx + i]}, Xj[4];
-      fb_actSE3(tij, qij, Xi, Xj);
-      out[i] = fx * (Xj[0] / Xj[2]) + cx;
-      out[PPx + i] = fy * (Xj[1] / Xj[2]) + cy;
-    }
-  }
-}
-
-// devo/projective_ops.py:53-105 fused: iproj (per-frame intrinsics of frame i) -> Gij = Gj * Gi^-1 (lietorch
-// semantics: quaternions renormalised on load) -> act4 -> proj (intrinsics of frame j, Z clamped at 0.1).
-// PP3: P == 3, the pixel loop is unrolled — the 27 patch values of an edge are requested together; with the run-time trip
-// count every pixel's three loads were waited for before the next pixel's were issued (nine round trips in a row).
-template <bool PP3>
-__global__ void k_transform(const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ intr,
-                            const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const int64_t* __restrict__ kk,
-                            float* __restrict__ c_pp2, float* __restrict__ c_2pp, float* __restrict__ valid,
-                            float* __restrict__ Ji, float* __restrict__ Jj, float* __restrict__ Jz, int E, int P, int flags,
-                            int* __restrict__ plan_bins, int plan_n2, int plan_H2, int plan_nb, int plan_D, int plan_ng, CorrPlanMode pm) {
-  const bool depth = flags & 1, tonly = flags & 2;
-  const int PPx = PP3 ? 9 : P * P, ctr = PP3 ? 4 : (P / 2) * P + P / 2, nc = depth ? 3 : 2;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int64_t fi = ii[e], fj = jj[e];
-    SE3<float> Gi = SE3<float>::load(poses + fi * 7), Gj = SE3<float>::load(poses + fj * 7);
-    SE3<float> G = Gj.mul(Gi.inv());
-    if (tonly) G.q = Q4<float>{0.0f, 0.0f, 0.0f, 1.0f};
-    const float fxi = intr[fi * 4], fyi = intr[fi * 4 + 1], cxi = intr[fi * 4 + 2], cyi = intr[fi * 4 + 3];
-    const float fxj = intr[fj * 4], fyj = intr[fj * 4 + 1], cxj = intr[fj * 4 + 2], cyj = intr[fj * 4 + 3];
-    const float* pk = patches + kk[e] * 3 * PPx;
-    float Xc = 0, Yc = 0, Zc = 1, Hc = 0;
-    int bx[9], by[9];                                            // integer pixels for the lookup's locality plan (P == 3)
-    float bcx = 0.0f, bcy = 0.0f;
-#pragma unroll
-    for (int i = 0; i < (PP3 ? 9 : PPx); i++) {
-      const float w = pk[2 * PPx + i];
-      V3<float> X0{(pk[i] - cxi) / fxi, (pk[PPx + i] - cyi) / fyi, 1.0f};
-      V3<float> X1 = qrot(G.q, X0) + w * G.t;
-      if (i == ctr) { Xc = X1.x; Yc = X1.y; Zc = X1.z; Hc = w; }
-      const float d = 1.0f / fmaxf(X1.z, 0.1f);
-      const float u = fxj * (d * X1.x) + cxj, v = fyj * (d * X1.y) + cyj;
-      if (c_pp2) { float* o = c_pp2 + ((int64_t)e * PPx + i) * nc; o[0] = u; o[1] = v; if (depth) o[2] = d; }
-      if (c_2pp) { c_2pp[(int64_t)e * 2 * PPx + i] = u; c_2pp[(int64_t)e * 2 * PPx + PPx + i] = v; }
-      if (plan_bins && i < 9) { bx[i] = corr_floor_to_int(u); by[i] = corr_floor_to_int(v); if (i == 4) { bcx = u; bcy = v; } }
-    }
-    // the lookup's plan bins, while the coordinates are still in registers (saves the plan's own pass over coords)
-    if (plan_bins) plan_bins[e] = corr_plan_bin(bx, by, bcx, bcy, 0, (int)fj, plan_n2, plan_H2, plan_nb, plan_D, plan_ng, pm.W2, pm.l1,
-                                                pm.heavy_cells, pm.dead_bin);
-    if (valid) valid[e] = (Zc > 0.2f) ? 1.0f : 0.0f;
-    if (Jj) {
-      const float d = (fabsf(Zc) > 0.2f) ? 1.0f / Zc : 0.0f;
-      float J[2][6] = {{fxj * d * Hc, 0.0f, -fxj * Xc * d * d * Hc, -fxj * Xc * d * d * Yc, fxj * d * Zc + fxj * Xc * d * d * Xc, -fxj * d * Yc},
-                       {0.0f, fyj * d * Hc, -fyj * Yc * d * d * Hc, -fyj * d * Zc - fyj * Yc * d * d * Yc, fyj * Yc * d * d * Xc, fyj * d * Xc}};
-#pragma unroll
-      for (int r = 0; r < 2; r++) {
-        float a[6];
-        G.adjT(J[r], a);
-#pragma unroll
-        for (int c = 0; c < 6; c++) { Jj[((int64_t)e * 2 + r) * 6 + c] = J[r][c]; if (Ji) Ji[((int64_t)e * 2 + r) * 6 + c] = -a[c]; }
-      }
-      if (Jz) {
-        Jz[(int64_t)e * 2] = fxj * d * G.t.x - fxj * Xc * d * d * G.t.z;
-        Jz[(int64_t)e * 2 + 1] = fyj * d * G.t.y - fyj * Yc * d * d * G.t.z;
-      }
-    }
-  }
-}
-
-// ------------------------------------------------------------------------------------------------- neighbors
-// ------------------------------------------------------------------------------------------------- adjoint of k_transform
-// devo_transform_vjp: gradients of everything k_transform outputs — the reprojected coordinates of all P*P pixels AND the
-// Jacobians Ji, Jj, Jz of the centre pixel (so the differentiable BA's second Gauss-Newton step gets its second-order terms,
-// exactly what autograd derives for devo/projective_ops.py:53-105) — with respect to poses[ii], poses[jj] (6-vectors of the left
-// perturbation G <- Exp(xi) G, lietorch's gradient convention: first 6 of the 7 slots) and patches[kk] (x, y, inverse depth of
-// every pixel).  One thread per edge evaluates the SAME arithmetic as k_transform on dual numbers, once per input direction
-// (12 pose directions over all pixels, 3 directions per pixel over that pixel), and adds  <cotangent, directional derivative>
-// into the gradient buffers with float atomics: no hand-derived reverse mode to get wrong, ~20 kFLOP per edge.
-struct Dual { float v, d; DEVO_HD Dual() : v(0.0f), d(0.0f) {} DEVO_HD Dual(float a) : v(a), d(0.0f) {} DEVO_HD Dual(float a, float b) : v(a), d(b) {} };
-DEVO_HD Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.d + b.d}; }
-DEVO_HD Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.d - b.d}; }
-DEVO_HD Dual operator-(Dual a) { return {-a.v, -a.d}; }
-DEVO_HD Dual operator*(Dual a, Dual b) { return {a.v * b.v, a.v * b.d + a.d * b.v}; }
-DEVO_HD Dual operator/(Dual a, Dual b) { const float r = 1.0f / b.v; return {a.v * r, (a.d - a.v * r * b.d) * r}; }
-DEVO_HD Dual operator+(float a, Dual b) { return {a + b.v, b.d}; }
-DEVO_HD Dual operator+(Dual a, float b) { return {a.v + b, a.d}; }
-DEVO_HD Dual operator-(float a, Dual b) { return {a - b.v, -b.d}; }
-DEVO_HD Dual operator-(Dual a, float b) { return {a.v - b, a.d}; }
-DEVO_HD Dual operator*(float a, Dual b) { return {a * b.v, a * b.d}; }
-DEVO_HD Dual operator*(Dual a, float b) { return {a.v * b, a.d * b}; }
-DEVO_HD Dual operator/(Dual a, float b) { return {a.v / b, a.d / b}; }
-template <> DEVO_HD Dual t_sqrt<Dual>(Dual x) { const float r = sqrtf(x.v); return {r, 0.5f * x.d / r}; }
-
-DEVO_HD float vof(float x) { return x; }
-DEVO_HD float vof(Dual x) { return x.v; }
-// the pixel part of k_transform: reprojection of one patch pixel (px, py, inverse depth w) -> (u, v, d) and the point X1
-template <typename S>
-DEVO_HD void tf_pixel(const SE3<S>& G, S px, S py, S w, const float* ki, const float* kj, S& u, S& v, S& d, V3<S>& X1) {
-  V3<S> X0{(px - ki[2]) / ki[0], (py - ki[3]) / ki[1], S(1.0f)};
-  X1 = qrot(G.q, X0) + w * G.t;
-  const S z = X1.z;
-  d = S(1.0f) / (vof(z) < 0.1f ? S(0.1f) : z);                            // Z.clamp(min = 0.1)  (projective_ops.py:43)
-  u = kj[0] * (d * X1.x) + kj[2];
-  v = kj[1] * (d * X1.y) + kj[3];
-}
-// the Jacobian part (projective_ops.py:75-103): J[0..11] = Ji (2x6), J[12..23] = Jj, J[24..25] = Jz
-// `traw` = the translation as projective_ops.py:97 reads it: the last column of Gij.matrix(), i.e. through the group action — its
-// derivative is that of Gij's translation under the left perturbation (d tau + d phi x t).  (Until round 5 this kernel seeded it with
-// d tau only, as if the reference sliced Gij.data: two chained Gauss-Newton steps differed from the reference's gradients by a few per
-// cent; tests/test_gpu_train_iteration.py pins the composition now.)
-template <typename S>
-DEVO_HD void tf_jacobians(const SE3<S>& G, const V3<S>& traw, const V3<S>& Xc, S Hc, const float* kj, S* J) {
-  const S X = Xc.x, Y = Xc.y, Z = Xc.z;
-  const float az = vof(Z) < 0.0f ? -vof(Z) : vof(Z);
-  const S d = az > 0.2f ? S(1.0f) / Z : S(0.0f);
-  const float fx = kj[0], fy = kj[1];
-  S Jj[2][6] = {{fx * d * Hc, S(0.0f), -(fx * X * d * d * Hc), -(fx * X * d * d * Y), fx * d * Z + fx * X * d * d * X, -(fx * d * Y)},
-                {S(0.0f), fy * d * Hc, -(fy * Y * d * d * Hc), -(fy * d * Z) - fy * Y * d * d * Y, fy * Y * d * d * X, fy * d * X}};
-#pragma unroll
-  for (int r = 0; r < 2; r++) {
-    S a[6];
-    G.adjT(Jj[r], a);
-#pragma unroll
-    for (int c = 0; c < 6; c++) { J[6 * r + c] = -a[c]; J[12 + 6 * r + c] = Jj[r][c]; }
-  }
-  J[24] = fx * d * traw.x - fx * X * d * d * traw.z;
-  J[25] = fy * d * traw.y - fy * Y * d * d * traw.z;
-}
-
-__global__ void k_transform_vjp(const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ intr,
-                                const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, const int64_t* __restrict__ kk,
-                                const float* __restrict__ g_c, const float* __restrict__ g_Ji, const float* __restrict__ g_Jj,
-                                const float* __restrict__ g_Jz, int E, int P, int flags, float* __restrict__ gposes,
-                                float* __restrict__ gpatches) {
-  const bool depth = flags & 1, tonly = flags & 2;
-  const int PPx = P * P, ctr = (P / 2) * P + P / 2, nc = depth ? 3 : 2;
-  const bool jac = g_Jj != nullptr;
-  // pose gradients: thousands of edges share a handful of frames — collected per workgroup in LDS (frames < VJP_LDS_FRAMES),
-  // ONE global atomic per touched (frame, component) and workgroup at the end
-  constexpr int VJP_LDS_FRAMES = 128;
-  __shared__ float s_gp[VJP_LDS_FRAMES][6];
-  for (int i = threadIdx.x; i < VJP_LDS_FRAMES * 6; i += blockDim.x) (&s_gp[0][0])[i] = 0.0f;
-  __syncthreads();
-  auto add_pose = [&](int64_t f, int c, float v) {
-    if (f < VJP_LDS_FRAMES) atomicAdd(&s_gp[f][c], v); else atomicAdd(gposes + f * 7 + c, v);
-  };
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int64_t fi = ii[e], fj = jj[e], k = kk[e];
-    const float* pi = poses + fi * 7;
-    const float* pj = poses + fj * 7;
-    const float* ki = intr + fi * 4;
-    const float* kj = intr + fj * 4;
-    const float* pk = patches + k * 3 * PPx;
-    const float* gc = g_c ? g_c + (int64_t)e * PPx * nc : nullptr;
-    float gJ[26];
-#pragma unroll
-    for (int c = 0; c < 12; c++) { gJ[c] = (jac && g_Ji) ? g_Ji[(int64_t)e * 12 + c] : 0.0f; gJ[12 + c] = jac ? g_Jj[(int64_t)e * 12 + c] : 0.0f; }
-    gJ[24] = (jac && g_Jz) ? g_Jz[(int64_t)e * 2] : 0.0f; gJ[25] = (jac && g_Jz) ? g_Jz[(int64_t)e * 2 + 1] : 0.0f;
-    // <cotangent, d outputs> of one pixel / of the Jacobians
-    auto pix_dot = [&](const SE3<Dual>& G, int i, Dual px, Dual py, Dual w, V3<Dual>& X1) -> float {
-      Dual u, v, d;
-      tf_pixel<Dual>(G, px, py, w, ki, kj, u, v, d, X1);
-      if (!gc) return 0.0f;
-      float s = gc[i * nc] * u.d + gc[i * nc + 1] * v.d;
-      if (depth) s += gc[i * nc + 2] * d.d;
-      return s;
-    };
-    auto jac_dot = [&](const SE3<Dual>& G, const V3<Dual>& traw, const V3<Dual>& Xc, Dual Hc) -> float {
-      if (!jac) return 0.0f;
-      Dual J[26];
-      tf_jacobians<Dual>(G, traw, Xc, Hc, kj, J);
-      float s = 0.0f;
-#pragma unroll
-      for (int c = 0; c < 26; c++) s += gJ[c] * J[c].d;
-      return s;
-    };
-    // G = Gj * Gi^-1 exactly as k_transform forms it
-    SE3<float> G0;
-    {
-      SE3<float> Gi = SE3<float>::load(pi), Gj = SE3<float>::load(pj);
-      G0 = Gj.mul(Gi.inv());
-      if (tonly) G0.q = Q4<float>{0.0f, 0.0f, 0.0f, 1.0f};
-    }
-    auto lift = [](const SE3<float>& X) -> SE3<Dual> {
-      SE3<Dual> Y;
-      Y.t = {Dual(X.t.x), Dual(X.t.y), Dual(X.t.z)};
-      Y.q = {Dual(X.q.x), Dual(X.q.y), Dual(X.q.z), Dual(X.q.w)};
-      return Y;
-    };
-    // ---- directions of Gij: xi = unit vector c of (tau, phi), Gij <- Exp(eps xi) Gij:  dt = tau + phi x t,  dq = 1/2 (phi, 0) (x) q.
-    //      Gij = Gj Gi^-1, so the same gradient belongs to pose j and  -Adj(Gij)^T  of it to pose i (the Mul / Inv rules of
-    //      lietorch_gpu.cu).
-    float gij[6];
-#pragma unroll 1
-    for (int c = 0; c < 6; c++) {
-      SE3<Dual> G = lift(G0);
-      if (c < 3) { (c == 0 ? G.t.x : c == 1 ? G.t.y : G.t.z).d = 1.0f; }
-      else {
-        float ph[3] = {0.0f, 0.0f, 0.0f};
-        ph[c - 3] = 1.0f;
-        const float tx = G0.t.x, ty = G0.t.y, tz = G0.t.z;
-        G.t.x.d = ph[1] * tz - ph[2] * ty; G.t.y.d = ph[2] * tx - ph[0] * tz; G.t.z.d = ph[0] * ty - ph[1] * tx;
-        const float qx = G0.q.x, qy = G0.q.y, qz = G0.q.z, qw = G0.q.w;
-        G.q.x.d = 0.5f * (ph[0] * qw + ph[1] * qz - ph[2] * qy);
-        G.q.y.d = 0.5f * (ph[1] * qw + ph[2] * qx - ph[0] * qz);
-        G.q.z.d = 0.5f * (ph[2] * qw + ph[0] * qy - ph[1] * qx);
-        G.q.w.d = 0.5f * (-ph[0] * qx - ph[1] * qy - ph[2] * qz);
-      }
-      float s = 0.0f;
-      V3<Dual> Xc{Dual(0.0f), Dual(0.0f), Dual(1.0f)};
-      for (int i = 0; i < PPx; i++) {
-        V3<Dual> X1;
-        s += pix_dot(G, i, Dual(pk[i]), Dual(pk[PPx + i]), Dual(pk[2 * PPx + i]), X1);
-        if (i == ctr) Xc = X1;
-      }
-      s += jac_dot(G, G.t, Xc, Dual(pk[2 * PPx + ctr]));     // (the translation in Jz moves with tau AND with phi: it is read through Gij.matrix())
-      gij[c] = s;
-    }
-    {
-      float gi[6];
-      G0.adjT(gij, gi);
-#pragma unroll
-      for (int c = 0; c < 6; c++) { add_pose(fj, c, gij[c]); add_pose(fi, c, -gi[c]); }
-    }
-    // ---- patch directions: pixel i, component x / y / inverse depth
-    {
-      const SE3<Dual> G = lift(G0);
-#pragma unroll 1
-      for (int i = 0; i < PPx; i++) {
-#pragma unroll 1
-        for (int comp = 0; comp < 3; comp++) {
-          Dual px(pk[i]), py(pk[PPx + i]), w(pk[2 * PPx + i]);
-          (comp == 0 ? px : comp == 1 ? py : w).d = 1.0f;
-          V3<Dual> X1;
-          float s = pix_dot(G, i, px, py, w, X1);
-          if (i == ctr) s += jac_dot(G, G.t, X1, w);
-          atomicAdd(gpatches + k * 3 * PPx + comp * PPx + i, s);
-        }
-      }
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < VJP_LDS_FRAMES * 6; i += blockDim.x) {
-    const float v = (&s_gp[0][0])[i];
-    if (v != 0.0f) atomicAdd(gposes + (i / 6) * 7 + i % 6, v);
-  }
-}
-
-__device__ __forceinline__ unsigned hash64(unsigned long long k) {
-  k ^= k >> 33; k *= 0xff51afd7ed558ccdULL; k ^= k >> 33; k *= 0xc4ceb9fe1a85ec53ULL; k ^= k >> 33;
-  return (unsigned)k;
-}
-__global__ void k_hash_group(const int64_t* __restrict__ ii, int E, unsigned long long* keys, unsigned cap_mask, int* slot_of, int* counts) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const unsigned long long key = (unsigned long long)ii[e];
-    unsigned h = hash64(key) & cap_mask;
-    for (;;) {
-      unsigned long long prev = atomicCAS(&keys[h], ~0ULL, key);
-      if (prev == ~0ULL || prev == key) break;
-      h = (h + 1) & cap_mask;
-    }
-    slot_of[e] = (int)h;
-    atomicAdd(&counts[h], 1);
-  }
-}
-// Where every group's edge list starts (round 6): the hash slots' counts become start offsets through ONE atomic per workgroup of 1 024 slots — a bump
-// allocator — instead of an exclusive scan of all 2 E slots by a single workgroup (33 of the call's 69 us at 45 312 edges).  Which group lies where in
-// `perm` depends on the order of the atomics; what the neighbours kernel reads from it does not.
-__global__ __launch_bounds__(1024) void k_group_alloc(int* __restrict__ counts, int cap, int* __restrict__ total) {
-  __shared__ int s_w[16];
-  __shared__ int s_base;
-  const int i = blockIdx.x * 1024 + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int c = i < cap ? counts[i] : 0;
-  const int inc = wave_inclusive_sum(c);
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int w = 0; w < 16; w++) { const int t = s_w[w]; s_w[w] = run; run += t; }
-    s_base = run ? atomicAdd(total, run) : 0;
-  }
-  __syncthreads();
-  if (i < cap) counts[i] = s_base + s_w[wave] + inc - c;
-}
-// ba.cpp:127-139: within the edges that share ii, order by (jj, edge index); previous / next or -1.
-__global__ void k_neighbors(const int64_t* __restrict__ jj, int E, const int* __restrict__ slot_of, const int* __restrict__ start,
-                            const int* __restrict__ count, const int* __restrict__ perm, int64_t* __restrict__ ix, int64_t* __restrict__ jx) {
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int s = slot_of[e], a = start[s], b = a + count[s];
-    const int64_t je = jj[e];
-    int64_t pj = 0, nj = 0; int pe = -1, ne = -1;
-    for (int q = a; q < b; q++) {
-      const int o = perm[q];
-      if (o == e) continue;
-      const int64_t jo = jj[o];
-      const bool less = (jo < je) || (jo == je && o < e);
-      if (less) { if (pe < 0 || jo > pj || (jo == pj && o > pe)) { pe = o; pj = jo; } }
-      else      { if (ne < 0 || jo < nj || (jo == nj && o < ne)) { ne = o; nj = jo; } }
-    }
-    ix[e] = pe; jx[e] = ne;
-  }
-}
-
-// ------------------------------------------------------------------------------------------------- workspace
-struct BaLayout {
-  size_t meta, rank, counts, cursor, ku, perm_a, perm_b, kx, range, partials, S, y, dX, patch_rec, edge_ej, prec, ybar, total, partials_bytes;
-  int max_seg, n_part;
-};
-// Waves per workgroup of the register-path accumulate kernel (N <= 16): what 160 KB of LDS hold — WAVES slabs + scratch + the atomic-path
-// system.  (Above 16 poses: the 4 that size the general kernel's partials.)
-static int acc_waves(int N) { return N <= 11 ? 8 : N <= 14 ? 6 : 4; }
+// ------------------------------------------------------------------------------------------------- host: kernel choice
 static size_t acc_reg_lds_bytes(int N) {
   const size_t n6 = 6 * (size_t)N, waves = acc_waves(N);
   return sizeof(float) * (n6 * (n6 + 1) + n6 + waves * n6 + 4 + waves * SCR_ROWS * SCR_LD + waves * ((size_t)N * (N + 1) / 2 * 36 + n6));
@@ -2495,130 +1642,15 @@ static acc_fn_t acc_reg_fn(int N) {
          (N <= 14) ? k_ba_accumulate_reg<14, 6, true> : k_ba_accumulate_reg<16, 4, true>;
 }
 
-static BaLayout ba_layout(int E, int Np, int N) {
-  BaLayout L;
-  size_t off = 0;
-  auto take = [&](size_t bytes) { size_t o = off; off += align_up(bytes); return o; };
-  L.max_seg = E < Np ? E : Np;
-  if (L.max_seg < 1) L.max_seg = 1;
-  const int waves = acc_waves(N);
-  int want = (L.max_seg + waves - 1) / waves;
-  L.n_part = want < ACC_MAX_WG ? (want < 1 ? 1 : want) : ACC_MAX_WG;
-  const size_t n6 = 6 * (size_t)N;
-  L.meta = take(sizeof(BaMeta));
-  L.rank = take(sizeof(int) * ((size_t)Np + 1));
-  L.counts = take(sizeof(int) * ((size_t)L.max_seg + 1));
-  L.cursor = take(sizeof(int) * (size_t)L.max_seg);
-  L.ku = take(sizeof(int) * (size_t)(E > 0 ? E : 1));
-  L.perm_a = take(sizeof(int) * (size_t)(E > 0 ? E : 1));
-  L.perm_b = take(sizeof(int) * (size_t)(E > 0 ? E : 1));
-  L.kx = take(sizeof(int) * (size_t)L.max_seg);
-  L.range = take(sizeof(int) * 4);                                  // the multi-kernel preparation's id range
-  L.partials_bytes = sizeof(float) * (size_t)L.n_part * (n6 * (n6 + 1) + n6 + 1);
-  if (N > BA_MAXN_LDS) {                                            // no partial systems: the area only holds k_ba_schur's partial tiles
-    const size_t nt = (n6 + 1 + SCH_T - 1) / SCH_T, ntile = nt * (nt + 1) / 2, nchunk = ((size_t)L.max_seg + SCH_K - 1) / SCH_K;
-    L.partials_bytes = sizeof(float) * ntile * nchunk * SCH_T * SCH_T;
-    if (L.partials_bytes > ((size_t)64 << 20)) L.partials_bytes = 16;   // (k_ba_schur then adds with atomics)
-  }
-  L.partials = take(L.partials_bytes);
-  L.S = take(sizeof(float) * ((n6 + 1) * (n6 + 1) + 1));
-  L.y = take(sizeof(float) * (n6 + 1));
-  L.dX = take(sizeof(float) * (n6 + 1));
-  L.patch_rec = take(sizeof(float) * 2 * (size_t)L.max_seg);
-  L.edge_ej = take(sizeof(float) * (size_t)L.max_seg * (n6 > 0 ? n6 : 1));      // E column of every patch
-  L.prec = take(sizeof(float) * 8 * (size_t)L.max_seg);                          // backward of devo_ba_solve_terms: per-patch adjoints
-  L.ybar = take(sizeof(float) * (n6 + 1));
-  L.total = off;
-  return L;
-}
-
-static unsigned next_pow2(unsigned v) { unsigned p = 1; while (p < v) p <<= 1; return p; }
-
 }  // namespace devo
 
 using namespace devo;
 
 extern "C" {
+// ------------------------------------------------------------------------------------------------- host: devo_ba_forward*
 size_t devo_ba_workspace_bytes(int E, int Np, int N) {
   if (E < 0 || Np < 0 || N < 0 || N > BA_MAXN) return 0;
   return ba_layout(E, Np, N).total;
-}
-
-// ---- graph preparation: kx = unique(kk) sorted, ku = inverse (ba_cuda.cu:435-437), edges grouped by patch
-// plan != NULL: also finish the lookup's locality plan (bins at plan + E + 1, see devo_transform) — in the same launch when
-// the single-workgroup path is taken, else with the plan's own kernel
-static int ba_prepare_impl(const int64_t* kk, int E, int Np, int N, void* ws, size_t ws_bytes, hipStream_t st,
-                           int* plan = nullptr, int plan_nbins = 0, int plan_starts = 0) {
-  const BaLayout L = ba_layout(E, Np, N);
-  if (ws == nullptr || ws_bytes < L.total) { set_error("devo_ba_prepare: workspace %zu < %zu bytes", ws_bytes, L.total); return DEVO_ERR_WORKSPACE; }
-  char* w = (char*)ws;
-  BaMeta* meta = (BaMeta*)(w + L.meta);
-  int* rank = (int*)(w + L.rank);
-  int* counts = (int*)(w + L.counts);
-  int* cursor = (int*)(w + L.cursor);
-  int* ku = (int*)(w + L.ku);
-  int* perm_a = (int*)(w + L.perm_a);
-  int* perm_b = (int*)(w + L.perm_b);
-  int* kx = (int*)(w + L.kx);
-  const size_t prep_lds = sizeof(int) * (1024 + PREP_FLAGS_LDS + 1 + 2 * PREP_SEGS_LDS + 1 + 8);
-  static PerDeviceOnce prep_attr;
-  if (prep_attr.first()) {
-    (void)hipFuncSetAttribute((const void*)k_ba_prepare<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    (void)hipFuncSetAttribute((const void*)k_ba_prepare<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    (void)hipFuncSetAttribute((const void*)k_ba_prepare<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    (void)hipFuncSetAttribute((const void*)k_ba_prepare<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    (void)hipFuncSetAttribute((const void*)k_ba_prepare<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-    (void)hipGetLastError();
-  }
-  // the single workgroup keeps up to 32 edges per thread in registers; beyond (DEVO's steady-state graph: 45 312 edges) its uncached passes and its
-  // 16 waves sorting 2 112 segments take 280 us where the multi-kernel path — on the id RANGE — takes 30 (DEVO_BA_PREP_MULTI_FROM: tuning switch)
-  static const int multi_from = [] { const char* e = getenv("DEVO_BA_PREP_MULTI_FROM"); return e ? atoi(e) : 32 * 1024 + 1; }();
-  if (E <= (1 << 17) && E < multi_from) {
-    typedef void (*prep_fn_t)(const int64_t*, int, int, int, BaMeta*, int*, int*, int*, int*, int*, int*, int*, int);
-    const int ept = (E + 1023) / 1024;                         // edges per thread
-    prep_fn_t prep = ept <= 8 ? k_ba_prepare<8> : ept <= 16 ? k_ba_prepare<16> : ept <= 24 ? k_ba_prepare<24> :
-                     ept <= 32 ? k_ba_prepare<32> : k_ba_prepare<0>;
-    if (plan && ept <= 32) {
-      typedef void (*both_fn_t)(const int64_t*, int, int, int, BaMeta*, int*, int*, int*, int*, int*, int*, int*, int, const int*, int, int*, int);
-      both_fn_t both = ept <= 8 ? k_prepare_and_order<8> : ept <= 16 ? k_prepare_and_order<16> : ept <= 24 ? k_prepare_and_order<24> :
-                       k_prepare_and_order<32>;
-      static PerDeviceOnce both_attr;
-      if (both_attr.first()) {
-        (void)hipFuncSetAttribute((const void*)k_prepare_and_order<8>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-        (void)hipFuncSetAttribute((const void*)k_prepare_and_order<16>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-        (void)hipFuncSetAttribute((const void*)k_prepare_and_order<24>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-        (void)hipFuncSetAttribute((const void*)k_prepare_and_order<32>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)prep_lds);
-        (void)hipGetLastError();
-      }
-      hipLaunchKernelGGL(both, dim3(1 + (unsigned)corr_order_workgroups(E, plan_nbins)), dim3(1024), prep_lds, st, kk, E, Np, L.max_seg, meta, rank,
-                         counts, cursor, ku, kx, perm_a, perm_b, ba_sig(E, N), plan + E + 1, plan_nbins, plan, plan_starts);
-      plan = nullptr;                                          // done
-    } else {
-      hipLaunchKernelGGL(prep, dim3(1), dim3(1024), prep_lds, st, kk, E, Np, L.max_seg, meta, rank, counts, cursor, ku, kx, perm_a, perm_b, ba_sig(E, N));
-    }
-  } else {
-    // (meta, rank, counts, cursor are contiguous at the head of the workspace)
-    int* range = (int*)(w + L.range);
-    if (hipMemsetAsync(w + L.meta, 0, L.ku - L.meta, st) != hipSuccess || hipMemsetAsync(range, 0x80, sizeof(int) * 4, st) != hipSuccess) {
-      (void)hipGetLastError(); set_error("devo_ba_prepare: memset failed"); return DEVO_ERR_LAUNCH;
-    }
-    const int eb = blocks_for(E, 256, 1024);
-    hipLaunchKernelGGL(k_kk_range, dim3(blocks_for(E, 256 * 4, 256)), dim3(256), 0, st, kk, E, Np, range);
-    hipLaunchKernelGGL(k_flag_ids_r, dim3(eb), dim3(256), 0, st, kk, E, Np, rank, range);
-    hipLaunchKernelGGL(k_excl_scan_dev, dim3(1), dim3(1024), 0, st, rank, range, 0, 0, &meta->n_seg);
-    hipLaunchKernelGGL(k_rank_edges_r, dim3(eb), dim3(256), 0, st, kk, E, Np, rank, ku, kx, counts, range, &meta->n_seg);
-    hipLaunchKernelGGL(k_excl_scan_dev, dim3(1), dim3(1024), 0, st, counts, &meta->n_seg, 1, L.max_seg, (int*)nullptr);
-    hipLaunchKernelGGL(k_scatter_edges_seg, dim3(eb), dim3(256), 0, st, ku, E, counts, cursor, perm_a, &meta->n_seg);
-    hipLaunchKernelGGL(k_sort_segments, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024)), dim3(256), 0, st, counts, meta, ba_sig(E, N), perm_a, perm_b);
-  }
-  if (plan) {                                                 // the plan's ordering step on its own
-    typedef void (*order_fn_t)(const int*, int, int, int*, int);
-    const long long per_thread = ((long long)E + ORDER_THREADS - 1) / ORDER_THREADS;
-    order_fn_t order_fn = per_thread <= 8 ? k_order_only<8> : per_thread <= 16 ? k_order_only<16> : per_thread <= 24 ? k_order_only<24> :
-                          per_thread <= 32 ? k_order_only<32> : per_thread <= 48 ? k_order_only<48> : per_thread <= 64 ? k_order_only<64> : k_order_only<0>;
-    hipLaunchKernelGGL(order_fn, dim3((unsigned)corr_order_workgroups(E, plan_nbins)), dim3(ORDER_THREADS), 0, st, plan + E + 1, E, plan_nbins, plan, plan_starts);
-  }
-  return check_launch("devo_ba_prepare");
 }
 
 // k_ba_schur + k_ba_damp behind k_ba_reduce(ep = BA_EP_DEFERRED): the Schur term of the general accumulate kernel as one product
@@ -2639,77 +1671,6 @@ static int ba_check_args(const char* who, int E, int Nbuf, int Np, int P, int t0
   return DEVO_OK;
 }
 
-int devo_ba_prepare(const int64_t* kk, int E, int Np, int N, void* ws, size_t ws_bytes, devo_stream_t stream) {
-  DEVO_REQUIRE(E >= 0 && Np > 0 && N >= 0, "devo_ba_prepare: bad sizes");
-  if (N > BA_MAXN) { set_error("devo_ba_prepare: %d optimised poses > %d supported", N, BA_MAXN); return DEVO_ERR_UNSUPPORTED; }
-  if (E == 0) return DEVO_OK;
-  return ba_prepare_impl(kk, E, Np, N, ws, ws_bytes, (hipStream_t)stream);
-}
-
-int devo_ba_prepared_tables(const void* ws, size_t ws_bytes, int E, int Np, int N, int* n_seg, int* kx, int* seg_start,
-                            int* perm, devo_stream_t stream) {
-  DEVO_REQUIRE(E > 0 && Np > 0 && N >= 0 && N <= BA_MAXN, "devo_ba_prepared_tables: bad sizes");
-  const BaLayout L = ba_layout(E, Np, N);
-  if (ws == nullptr || ws_bytes < L.total) { set_error("devo_ba_prepared_tables: workspace %zu < %zu bytes", ws_bytes, L.total); return DEVO_ERR_WORKSPACE; }
-  const char* w = (const char*)ws;
-  hipStream_t st = (hipStream_t)stream;
-  bool ok = true;
-  if (n_seg) ok = ok && hipMemcpyAsync(n_seg, w + L.meta + offsetof(BaMeta, n_seg), sizeof(int), hipMemcpyDeviceToDevice, st) == hipSuccess;
-  if (kx) ok = ok && hipMemcpyAsync(kx, w + L.kx, sizeof(int) * (size_t)L.max_seg, hipMemcpyDeviceToDevice, st) == hipSuccess;
-  if (seg_start) ok = ok && hipMemcpyAsync(seg_start, w + L.counts, sizeof(int) * ((size_t)L.max_seg + 1), hipMemcpyDeviceToDevice, st) == hipSuccess;
-  if (perm) ok = ok && hipMemcpyAsync(perm, w + L.perm_b, sizeof(int) * (size_t)E, hipMemcpyDeviceToDevice, st) == hipSuccess;
-  if (!ok) { (void)hipGetLastError(); set_error("devo_ba_prepared_tables: copy failed"); return DEVO_ERR_LAUNCH; }
-  return DEVO_OK;
-}
-
-// The index tables of one kk (n_seg, kx, segment starts, edges grouped by patch) from a workspace prepared for OTHER sizes of the same edge list —
-// devo_upd_graph_tables' (Np = its bound, N = 0) — into this one: one launch instead of the preparation's nine.  devo.py:311,337 hand the same
-// kk to the Update operator and, right behind it, to the BA.  Ids in [Np, src Np) exist as groups there and count as bad ids here (segment 0 of
-// devo_ba_prepare): such a source leaves the destination UNPREPARED (sig 0: the BA reports status -1) instead of different tables.
-__global__ __launch_bounds__(256) void k_import_tables(const BaMeta* __restrict__ smeta, const int* __restrict__ scounts, const int* __restrict__ sperm,
-                                                       const int* __restrict__ skx, int ssig, BaMeta* __restrict__ dmeta, int* __restrict__ dcounts,
-                                                       int* __restrict__ dperm, int* __restrict__ dkx, int E, int Np, int dmax_seg, int dsig) {
-  const int n = smeta->n_seg;
-  const bool ok = smeta->sig == ssig && n >= 0 && n <= dmax_seg && (n == 0 || skx[n - 1] < Np);
-  const int gid = blockIdx.x * blockDim.x + threadIdx.x, gsz = blockDim.x * gridDim.x;
-  if (gid == 0) { dmeta->n_seg = ok ? n : 0; dmeta->fail = 0; dmeta->sig = ok ? dsig : 0; dmeta->pad = ok ? smeta->pad : 0; }   // (pad: "perm is the identity")
-  if (!ok) return;
-  for (int i = gid; i <= dmax_seg; i += gsz) dcounts[i] = i <= n ? scounts[i] : E;
-  for (int i = gid; i < n; i += gsz) dkx[i] = skx[i];
-  for (int e = gid; e < E; e += gsz) dperm[e] = sperm[e];
-}
-
-int devo_ba_import_tables(const void* src_ws, size_t src_bytes, int src_Np, int src_N, void* ws, size_t ws_bytes, int E, int Np, int N,
-                          devo_stream_t stream) {
-  DEVO_REQUIRE(E > 0 && Np > 0 && N >= 0 && src_Np > 0 && src_N >= 0, "devo_ba_import_tables: bad sizes");
-  if (N > BA_MAXN || src_N > BA_MAXN) { set_error("devo_ba_import_tables: %d / %d optimised poses > %d supported", N, src_N, BA_MAXN); return DEVO_ERR_UNSUPPORTED; }
-  const BaLayout S = ba_layout(E, src_Np, src_N), D = ba_layout(E, Np, N);
-  if (src_ws == nullptr || src_bytes < S.total) { set_error("devo_ba_import_tables: source workspace %zu < %zu bytes", src_bytes, S.total); return DEVO_ERR_WORKSPACE; }
-  if (ws == nullptr || ws_bytes < D.total) { set_error("devo_ba_import_tables: workspace %zu < %zu bytes", ws_bytes, D.total); return DEVO_ERR_WORKSPACE; }
-  const char* s = (const char*)src_ws;
-  char* d = (char*)ws;
-  hipLaunchKernelGGL(k_import_tables, dim3(blocks_for(E, 256, 256)), dim3(256), 0, (hipStream_t)stream, (const BaMeta*)(s + S.meta), (const int*)(s + S.counts),
-                     (const int*)(s + S.perm_b), (const int*)(s + S.kx), ba_sig(E, src_N), (BaMeta*)(d + D.meta), (int*)(d + D.counts), (int*)(d + D.perm_b),
-                     (int*)(d + D.kx), E, Np, D.max_seg, ba_sig(E, N));
-  return check_launch("devo_ba_import_tables");
-}
-
-int devo_ba_prepare_plan(const int64_t* kk, int E, int Np, int N, void* ws, size_t ws_bytes, int* plan, int plan_frames,
-                         int plan_height, int plan_width, int plan_l1, devo_stream_t stream) {
-  DEVO_REQUIRE(E >= 0 && Np > 0 && N >= 0, "devo_ba_prepare_plan: bad sizes");
-  if (N > BA_MAXN) { set_error("devo_ba_prepare_plan: %d optimised poses > %d supported", N, BA_MAXN); return DEVO_ERR_UNSUPPORTED; }
-  DEVO_REQUIRE(plan != nullptr && plan_frames > 0 && plan_height > 0, "devo_ba_prepare_plan: missing plan");
-  if (E == 0) return DEVO_OK;
-  const CorrPlanGeom pg = corr_plan_geom(1, plan_frames, plan_height);
-  DEVO_REQUIRE(pg.nb > 0, "devo_ba_prepare_plan: too many frames for a locality plan (%d)", plan_frames);
-  if (plan_l1 >= 2) {                                         // GROUP plan (devo_corr_order): the bins' first slots go into the plan's tail
-    const long long nb = corr_grp_nbins(1, plan_frames, plan_height, plan_width, plan_l1);
-    DEVO_REQUIRE(nb > 0, "devo_ba_prepare_plan: no group plan for this geometry (%d frames of %d x %d)", plan_frames, plan_height, plan_width);
-    return ba_prepare_impl(kk, E, Np, N, ws, ws_bytes, (hipStream_t)stream, plan, (int)nb, 1);
-  }
-  return ba_prepare_impl(kk, E, Np, N, ws, ws_bytes, (hipStream_t)stream, plan, (int)corr_plan_nbins(1, plan_frames, pg));
-}
-
 int devo_ba_forward(float* poses, float* patches, const float* intrinsics, const float* target, const float* weight,
                     const float* lmbda, const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int Nbuf, int Np,
                     int P, int t0, int t1, int iterations, void* ws, size_t ws_bytes, int* status_flag,
@@ -2722,7 +1683,6 @@ int devo_ba_forward(float* poses, float* patches, const float* intrinsics, const
                                   iterations, ws, ws_bytes, status_flag, stream);
 }
 
-struct PlanRider { int* plan; int nbins; int starts; };          // a plan buffer whose bins devo_transform has written: ordered during the BA
 static int ba_forward_impl(float* poses, float* patches, const float* intrinsics, const TargetSrc target, const float* weight,
                            const float* lmbda, const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int Nbuf,
                            int Np, int P, int t0, int t1, int iterations, void* ws, size_t ws_bytes, int* status_flag,
@@ -2746,14 +1706,6 @@ int devo_ba_forward_prepared_delta(float* poses, float* patches, const float* in
                coords_xy_stride, coords_centre);
   return ba_forward_impl(poses, patches, intrinsics, TargetSrc{delta, coords, coords_edge_stride, coords_xy_stride, coords_centre},
                          weight, lmbda, ii, jj, kk, E, Nbuf, Np, P, t0, t1, iterations, ws, ws_bytes, status_flag, stream);
-}
-
-static void launch_order_only(hipStream_t st, int E, const PlanRider& r) {
-  typedef void (*order_fn_t)(const int*, int, int, int*, int);
-  const long long per_thread = ((long long)E + ORDER_THREADS - 1) / ORDER_THREADS;
-  order_fn_t order_fn = per_thread <= 8 ? k_order_only<8> : per_thread <= 16 ? k_order_only<16> : per_thread <= 24 ? k_order_only<24> :
-                        per_thread <= 32 ? k_order_only<32> : per_thread <= 48 ? k_order_only<48> : per_thread <= 64 ? k_order_only<64> : k_order_only<0>;
-  hipLaunchKernelGGL(order_fn, dim3((unsigned)corr_order_workgroups(E, r.nbins)), dim3(ORDER_THREADS), 0, st, r.plan + E + 1, E, r.nbins, r.plan, r.starts);
 }
 
 static int ba_forward_impl(float* poses, float* patches, const float* intrinsics, const TargetSrc target, const float* weight,
@@ -2876,16 +1828,9 @@ int devo_ba_forward_prepared_delta_plan(float* poses, float* patches, const floa
                "devo_ba_forward_prepared_delta_plan: coords %p, strides %d / %d, centre %d", (const void*)coords, coords_edge_stride,
                coords_xy_stride, coords_centre);
   DEVO_REQUIRE(plan != nullptr && plan_frames > 0 && plan_height > 0, "devo_ba_forward_prepared_delta_plan: missing plan");
-  PlanRider rider{plan, 0, 0};
-  const CorrPlanGeom pg = corr_plan_geom(1, plan_frames, plan_height);
-  DEVO_REQUIRE(pg.nb > 0, "devo_ba_forward_prepared_delta_plan: too many frames for a locality plan (%d)", plan_frames);
-  if (plan_l1 >= 2) {                                             // GROUP plan: the bins' first slots go into the plan's tail
-    const long long nb = corr_grp_nbins(1, plan_frames, plan_height, plan_width, plan_l1);
-    DEVO_REQUIRE(nb > 0, "devo_ba_forward_prepared_delta_plan: no group plan for this geometry (%d frames of %d x %d)", plan_frames, plan_height, plan_width);
-    rider.nbins = (int)nb; rider.starts = 1;
-  } else {
-    rider.nbins = (int)corr_plan_nbins(1, plan_frames, pg);
-  }
+  PlanRider rider;
+  int rc;
+  if ((rc = ba_plan_rider("devo_ba_forward_prepared_delta_plan", plan, plan_frames, plan_height, plan_width, plan_l1, &rider))) return rc;
   return ba_forward_impl(poses, patches, intrinsics, TargetSrc{delta, coords, coords_edge_stride, coords_xy_stride, coords_centre},
                          weight, lmbda, ii, jj, kk, E, Nbuf, Np, P, t0, t1, iterations, ws, ws_bytes, status_flag, stream, rider);
 }
@@ -2989,207 +1934,6 @@ int devo_ba_solve_terms_backward(const float* terms, const int64_t* ii, const in
   return check_launch("devo_ba_solve_terms_backward");
 }
 
-size_t devo_neighbors_workspace_bytes(int E) {
-  if (E <= 0) return 256;
-  const size_t cap = next_pow2((unsigned)(2 * (size_t)E));
-  return align_up(8 * cap) + align_up(4 * (cap + 1)) + align_up(4 * cap) + 2 * align_up(4 * (size_t)E);
-}
-
-int devo_ba_neighbors(const int64_t* ii, const int64_t* jj, int64_t* ix, int64_t* jx, int E, void* ws, size_t ws_bytes,
-                      devo_stream_t stream) {
-  if (E <= 0) return DEVO_OK;
-  const size_t need = devo_neighbors_workspace_bytes(E);
-  if (ws == nullptr || ws_bytes < need) { set_error("devo_ba_neighbors: workspace %zu < %zu bytes", ws_bytes, need); return DEVO_ERR_WORKSPACE; }
-  hipStream_t st = (hipStream_t)stream;
-  const size_t cap = next_pow2((unsigned)(2 * (size_t)E));
-  char* w = (char*)ws;
-  unsigned long long* keys = (unsigned long long*)w; w += align_up(8 * cap);
-  int* counts = (int*)w; w += align_up(4 * (cap + 1));
-  int* cursor = (int*)w; w += align_up(4 * cap);
-  int* slot_of = (int*)w; w += align_up(4 * (size_t)E);
-  int* perm = (int*)w;
-  if (hipMemsetAsync(keys, 0xFF, 8 * cap, st) != hipSuccess ||
-      hipMemsetAsync(counts, 0, (char*)slot_of - (char*)counts, st) != hipSuccess) { set_error("devo_ba_neighbors: memset failed"); return DEVO_ERR_LAUNCH; }
-  const int eb = blocks_for(E, 256, 1024);
-  hipLaunchKernelGGL(k_hash_group, dim3(eb), dim3(256), 0, st, ii, E, keys, (unsigned)(cap - 1), slot_of, counts);
-  hipLaunchKernelGGL(k_group_alloc, dim3((unsigned)((cap + 1023) / 1024)), dim3(1024), 0, st, counts, (int)cap, counts + cap);   // (counts[cap]: zeroed above)
-  hipLaunchKernelGGL(k_scatter_edges, dim3(eb), dim3(256), 0, st, slot_of, E, counts, cursor, perm);                // (cursor[s] ends as the group's size)
-  hipLaunchKernelGGL(k_neighbors, dim3(eb), dim3(256), 0, st, jj, E, slot_of, counts, cursor, perm, ix, jx);
-  return check_launch("devo_ba_neighbors");
-}
-
-// ---- the Update operator's graph tables in one call (round 6).  DEVO's inference hands the operator NEW ii / jj / kk tensors every frame
-// (devo.py:228-231, :304-306), so what devo_amd.update builds per graph — neighbours by patch, groups by patch, groups by frame pair
-// (enet.py:86-95) — is per-frame work: as torch ops + three separate preparations it was 250 us of a 1.2 ms frame (nine reductions / elementwise
-// kernels for the pair key, a hash grouping for the neighbours that repeats the patch grouping, eight table copies).
-// range[0..3] = max(-ii), max(ii), max(-jj), max(jj), all starting at 0x80808080.
-__global__ void k_pair_range(const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int E, int* __restrict__ range) {
-  int v[4] = {(int)0x80808080, (int)0x80808080, (int)0x80808080, (int)0x80808080};
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x) {
-    const int i = (int)ii[e], j = (int)jj[e];
-    v[0] = max(v[0], -i); v[1] = max(v[1], i); v[2] = max(v[2], -j); v[3] = max(v[3], j);
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-    for (int c = 0; c < 4; c++) v[c] = max(v[c], __shfl_xor(v[c], o));
-  __shared__ int s_r[4][4];
-  if ((threadIdx.x & 63) == 0)
-    for (int c = 0; c < 4; c++) s_r[c][threadIdx.x >> 6] = v[c];
-  __syncthreads();
-  if (threadIdx.x < 4) {
-    const int c = threadIdx.x;
-    atomicMax(&range[c], max(max(s_r[c][0], s_r[c][1]), max(s_r[c][2], s_r[c][3])));
-  }
-}
-// key = (ii - min ii) * (max jj - min jj + 1) + (jj - min jj): the groups of ii * 12345 + jj (enet.py:94), keys within (frames in the window)^2
-__global__ void k_pair_key(const int64_t* __restrict__ ii, const int64_t* __restrict__ jj, int E, const int* __restrict__ range, int64_t* __restrict__ key) {
-  const int imin = -range[0], jmin = -range[2], span = range[3] - jmin + 1;
-  for (int e = blockIdx.x * blockDim.x + threadIdx.x; e < E; e += blockDim.x * gridDim.x)
-    key[e] = (int64_t)((int)ii[e] - imin) * span + ((int)jj[e] - jmin);
-}
-// cuda_ba.neighbors (ba.cpp:127-139) from the PREPARED tables of the grouping key: one wave per segment, the members' (edge, jj) in the lanes.
-__global__ __launch_bounds__(256) void k_neighbors_seg(const int64_t* __restrict__ jj, const BaMeta* __restrict__ meta, const int* __restrict__ seg_start,
-                                                       const int* __restrict__ perm, int64_t* __restrict__ ix, int64_t* __restrict__ jx) {
-  const int lane = threadIdx.x & 63;
-  const int wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, nwaves = (blockDim.x * gridDim.x) >> 6;
-  const int n_seg = meta->n_seg;
-  for (int s = wave; s < n_seg; s += nwaves) {
-    const int a = seg_start[s], m = seg_start[s + 1] - a;
-    if (m <= 64) {
-      const int e = lane < m ? perm[a + lane] : -1;
-      const int je = lane < m ? (int)jj[e] : 0;
-      int pj = 0, nj = 0, pe = -1, ne = -1;
-      for (int q = 0; q < m; q++) {
-        const int o = __builtin_amdgcn_readlane(e, q), jo = __builtin_amdgcn_readlane(je, q);
-        if (o == e) continue;
-        const bool less = (jo < je) || (jo == je && o < e);
-        if (less) { if (pe < 0 || jo > pj || (jo == pj && o > pe)) { pe = o; pj = jo; } }
-        else      { if (ne < 0 || jo < nj || (jo == nj && o < ne)) { ne = o; nj = jo; } }
-      }
-      if (lane < m) { ix[e] = pe; jx[e] = ne; }
-    } else {
-      for (int i = lane; i < m; i += 64) {
-        const int e = perm[a + i];
-        const int64_t je = jj[e];
-        int64_t pj = 0, nj = 0; int pe = -1, ne = -1;
-        for (int q = a; q < a + m; q++) {
-          const int o = perm[q];
-          if (o == e) continue;
-          const int64_t jo = jj[o];
-          const bool less = (jo < je) || (jo == je && o < e);
-          if (less) { if (pe < 0 || jo > pj || (jo == pj && o > pe)) { pe = o; pj = jo; } }
-          else      { if (ne < 0 || jo < nj || (jo == nj && o < ne)) { ne = o; nj = jo; } }
-        }
-        ix[e] = pe; jx[e] = ne;
-      }
-    }
-  }
-}
-
-int devo_ba_table_offsets(int E, int Np, int N, size_t* offsets) {
-  DEVO_REQUIRE(E > 0 && Np > 0 && N >= 0 && N <= BA_MAXN && offsets != nullptr, "devo_ba_table_offsets: bad sizes");
-  const BaLayout L = ba_layout(E, Np, N);
-  offsets[0] = L.meta + offsetof(BaMeta, n_seg);
-  offsets[1] = L.kx;
-  offsets[2] = L.counts;
-  offsets[3] = L.perm_b;
-  offsets[4] = (size_t)L.max_seg;
-  return DEVO_OK;
-}
-
-int devo_upd_graph_tables(const int64_t* ii, const int64_t* jj, const int64_t* kk, int E, int bound, void* ws_kk, size_t ws_kk_bytes,
-                          void* ws_ij, size_t ws_ij_bytes, int64_t* pair_key, int64_t* ix, int64_t* jx, devo_stream_t stream) {
-  DEVO_REQUIRE(E >= 0 && bound > 0, "devo_upd_graph_tables: bad sizes");
-  if (E == 0) return DEVO_OK;
-  DEVO_REQUIRE(ii && jj && kk && ws_kk && ws_ij && pair_key, "devo_upd_graph_tables: missing argument");
-  hipStream_t st = (hipStream_t)stream;
-  int rc;
-  const BaLayout L = ba_layout(E, bound, 0);
-  // beyond the single-workgroup preparation's size (DEVO's steady-state graph: 45 312 edges) both edge lists go through the multi-kernel stages
-  // TOGETHER (Prep2): 11 launches for what the two preparations, their fills and the key's range fill did in 22
-  static const int multi_from = [] { const char* e = getenv("DEVO_BA_PREP_MULTI_FROM"); return e ? atoi(e) : 32 * 1024 + 1; }();
-  static const bool dual_env = [] { const char* e = getenv("DEVO_UPD_TABLES_DUAL"); return !(e && e[0] == '0'); }();
-  if (dual_env && !(E <= (1 << 17) && E < multi_from)) {
-    if (ws_kk_bytes < L.total || ws_ij_bytes < L.total) { set_error("devo_upd_graph_tables: workspace %zu / %zu < %zu bytes", ws_kk_bytes, ws_ij_bytes, L.total); return DEVO_ERR_WORKSPACE; }
-    char* w0 = (char*)ws_kk;
-    char* w1 = (char*)ws_ij;
-    Prep2 p;
-    const int64_t* keys[2] = {kk, pair_key};
-    char* wsp[2] = {w0, w1};
-    for (int y = 0; y < 2; y++) {
-      p.kk[y] = keys[y]; p.meta[y] = (BaMeta*)(wsp[y] + L.meta); p.rank[y] = (int*)(wsp[y] + L.rank); p.counts[y] = (int*)(wsp[y] + L.counts);
-      p.cursor[y] = (int*)(wsp[y] + L.cursor); p.ku[y] = (int*)(wsp[y] + L.ku); p.kx[y] = (int*)(wsp[y] + L.kx); p.perm_a[y] = (int*)(wsp[y] + L.perm_a);
-      p.perm_b[y] = (int*)(wsp[y] + L.perm_b); p.range[y] = (int*)(wsp[y] + L.range);
-    }
-    int* prange = (int*)(pair_key + E);                             // (the two extra words of the key buffer)
-    const long long n4 = (long long)((L.ku - L.meta) / 16);         // (every region of the layout is a multiple of 256 bytes)
-    hipLaunchKernelGGL(k_prep_clear2, dim3(blocks_for(n4, 256, 2048)), dim3(256), 0, st, (int4*)(w0 + L.meta), (int4*)(w1 + L.meta), n4, p.range[0], p.range[1], prange);
-    hipLaunchKernelGGL(k_pair_range, dim3(blocks_for(E, 256 * 4, 256)), dim3(256), 0, st, ii, jj, E, prange);
-    hipLaunchKernelGGL(k_pair_key, dim3(blocks_for(E, 256, 1024)), dim3(256), 0, st, ii, jj, E, prange, pair_key);
-    const unsigned eb = (unsigned)blocks_for(E, 256, 1024);
-    hipLaunchKernelGGL(k_kk_range2, dim3(blocks_for(E, 256 * 4, 256), 2), dim3(256), 0, st, p, E, bound);
-    hipLaunchKernelGGL(k_flag_ids_r2, dim3(eb, 2), dim3(256), 0, st, p, E, bound);
-    hipLaunchKernelGGL(k_excl_scan_dev2, dim3(1, 2), dim3(1024), 0, st, p, 0, 0);
-    hipLaunchKernelGGL(k_rank_edges_r2, dim3(eb, 2), dim3(256), 0, st, p, E, bound);
-    hipLaunchKernelGGL(k_excl_scan_dev2, dim3(1, 2), dim3(1024), 0, st, p, 1, L.max_seg);
-    hipLaunchKernelGGL(k_scatter_edges_seg2, dim3(eb, 2), dim3(256), 0, st, p, E);
-    hipLaunchKernelGGL(k_sort_segments2, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024), 2), dim3(256), 0, st, p, ba_sig(E, 0));
-    if (ix && jx)
-      hipLaunchKernelGGL(k_neighbors_seg, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024)), dim3(256), 0, st, jj, (const BaMeta*)(w0 + L.meta),
-                         (const int*)(w0 + L.counts), (const int*)(w0 + L.perm_b), ix, jx);
-    return check_launch("devo_upd_graph_tables");
-  }
-  if ((rc = ba_prepare_impl(kk, E, bound, 0, ws_kk, ws_kk_bytes, st))) return rc;
-  if (ix && jx) {
-    const char* w = (const char*)ws_kk;
-    hipLaunchKernelGGL(k_neighbors_seg, dim3(blocks_for((long long)L.max_seg * 64, 256, 1024)), dim3(256), 0, st, jj, (const BaMeta*)(w + L.meta),
-                       (const int*)(w + L.counts), (const int*)(w + L.perm_b), ix, jx);
-  }
-  int* range = (int*)(pair_key + E);                                // (the two extra words of the key buffer)
-  if (hipMemsetAsync(range, 0x80, sizeof(int) * 4, st) != hipSuccess) { (void)hipGetLastError(); set_error("devo_upd_graph_tables: memset failed"); return DEVO_ERR_LAUNCH; }
-  hipLaunchKernelGGL(k_pair_range, dim3(blocks_for(E, 256 * 4, 256)), dim3(256), 0, st, ii, jj, E, range);
-  hipLaunchKernelGGL(k_pair_key, dim3(blocks_for(E, 256, 1024)), dim3(256), 0, st, ii, jj, E, range, pair_key);
-  if ((rc = ba_prepare_impl(pair_key, E, bound, 0, ws_ij, ws_ij_bytes, st))) return rc;
-  return check_launch("devo_upd_graph_tables");
-}
-
-int devo_ba_reproject(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj,
-                      const int64_t* kk, float* coords, int E, int P, devo_stream_t stream) {
-  if (E <= 0) return DEVO_OK;
-  hipLaunchKernelGGL(k_reproject, dim3(blocks_for(E, 128, 4096)), dim3(128), 0, (hipStream_t)stream, poses, patches, intrinsics, ii, jj, kk, coords, E, P);
-  return check_launch("devo_ba_reproject");
-}
-
-int devo_transform(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj,
-                   const int64_t* kk, float* coords_pp2, float* coords_2pp, float* valid, float* Ji, float* Jj, float* Jz, int E,
-                   int P, int flags, int* plan, int plan_frames, int plan_height, int plan_radius, int plan_width, int plan_l1,
-                   devo_stream_t stream) {
-  if (E <= 0) return DEVO_OK;
-  DEVO_REQUIRE(!(Ji || Jz) || Jj, "devo_transform: Jj must be requested together with Ji / Jz");
-  int nb = 0;
-  CorrPlanMode pm{0, 0, 0, -1};
-  if (plan) {
-    DEVO_REQUIRE(P == 3 && plan_frames > 0 && plan_height > 0 && plan_radius >= 0 && plan_radius <= 5, "devo_transform: bad plan geometry");
-    DEVO_REQUIRE(plan_l1 == 0 || (plan_l1 >= 2 && plan_width > 0), "devo_transform: a group plan needs the level's width and an integer level ratio >= 2");
-    const CorrPlanGeom pg = corr_plan_geom(1, plan_frames, plan_height);
-    DEVO_REQUIRE(pg.nb > 0, "devo_transform: too many frames for a locality plan (%d)", plan_frames);
-    nb = corr_plan_pack(pg);
-    const long long nbins = plan_l1 >= 2 ? corr_grp_nbins(1, plan_frames, plan_height, plan_width, plan_l1) : corr_plan_nbins(1, plan_frames, pg);
-    if (plan_l1 >= 2 && (nbins == 0 || plan_radius != 3)) {
-      set_error("devo_transform: no group plan for this geometry (radius 3 only, at most %d groups: %d frames of %d x %d)", CORR_ORDER_MAXBINS, plan_frames, plan_height, plan_width);
-      return DEVO_ERR_UNSUPPORTED;
-    }
-    pm = CorrPlanMode{plan_width, plan_l1, 16 * corr_region_tmax(plan_radius), (int)nbins - 1};
-  }
-  constexpr int tblock = 64;                                      // (64 / 128 / 256 threads: 7.40 / 7.78 / 8.28 us at cfg2)
-  hipLaunchKernelGGL(P == 3 ? k_transform<true> : k_transform<false>, dim3(blocks_for(E, tblock, 4096)), dim3(tblock), 0, (hipStream_t)stream, poses, patches, intrinsics, ii, jj,
-                     kk, coords_pp2, coords_2pp, valid, Ji, Jj, Jz, E, P, flags, plan ? plan + E + 1 : nullptr, plan_frames, plan_height,
-                     nb, 2 * plan_radius + 2, plan_radius <= 3 ? 1 : 3, pm);
-  return check_launch("devo_transform");
-}
-
-
 // devo/ba.py:95-106 in one kernel (training): the 30 per-edge numbers devo_ba_solve_terms takes, from transform's outputs.
 //   r = gate * (target - centre),  w = gate * weight,  gate = valid * [|target - centre| < 250] * [centre inside bounds]
 //   terms[e] = r(2) | w(2) | Jz(2) | -Ji(12) | Jj(12)
@@ -3253,21 +1997,6 @@ int devo_ba_edge_terms_backward(const float* g_terms, const float* gate, int E, 
   hipLaunchKernelGGL(k_ba_edge_terms_bwd, dim3(blocks_for(E, 256, 1 << 20)), dim3(256), 0, st, g_terms, gate, E, P, g_coords, g_target, g_weight, g_Ji,
                      g_Jj, g_Jz);
   return check_launch("devo_ba_edge_terms_backward");
-}
-
-int devo_transform_vjp(const float* poses, const float* patches, const float* intrinsics, const int64_t* ii, const int64_t* jj,
-                       const int64_t* kk, const float* g_coords, const float* g_Ji, const float* g_Jj, const float* g_Jz, int E,
-                       int Nbuf, int Np, int P, int flags, float* g_poses, float* g_patches, devo_stream_t stream) {
-  DEVO_REQUIRE(E >= 0 && Nbuf > 0 && Np > 0 && P > 0 && P * P <= 25, "devo_transform_vjp: bad sizes");
-  DEVO_REQUIRE(g_poses && g_patches, "devo_transform_vjp: missing gradient buffers");
-  DEVO_REQUIRE(!(g_Ji || g_Jz) || g_Jj, "devo_transform_vjp: the Jacobian cotangents come together with g_Jj");
-  hipStream_t st = (hipStream_t)stream;
-  if (hipMemsetAsync(g_poses, 0, sizeof(float) * 7 * (size_t)Nbuf, st) != hipSuccess ||
-      hipMemsetAsync(g_patches, 0, sizeof(float) * 3 * (size_t)Np * P * P, st) != hipSuccess) { set_error("devo_transform_vjp: memset failed"); return DEVO_ERR_LAUNCH; }
-  if (E == 0) return DEVO_OK;
-  hipLaunchKernelGGL(k_transform_vjp, dim3(blocks_for(E, 128, 8192)), dim3(128), 0, st, poses, patches, intrinsics, ii, jj, kk, g_coords, g_Ji,
-                     g_Jj, g_Jz, E, P, flags, g_poses, g_patches);
-  return check_launch("devo_transform_vjp");
 }
 
 }  // extern "C"

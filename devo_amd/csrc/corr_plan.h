@@ -1,6 +1,6 @@
-// The locality plan's ordering step as a device function: corr.hip wraps it into corr_order_kernel, ba.hip runs it as the
+// The locality plan's ordering step as a device function: corr.hip wraps it into corr_order_kernel, ba_tables.hip runs it as the
 // workgroups 1 .. G of k_prepare_and_order (next to the BA's index preparation in workgroup 0: latency-bound kernels that do
-// not depend on each other).
+// not depend on each other) and as k_order_only, ba.hip behind the solving workgroups of k_ba_solve_retract_order.
 #pragma once
 #include "corr_tile.h"
 #include <stdlib.h>

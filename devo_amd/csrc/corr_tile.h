@@ -1,5 +1,5 @@
 // Tile geometry of the staged lookup kernel and the plan's bin of an edge — shared by corr.hip (lookup + plan kernels)
-// and ba.hip (the fused reprojection can emit the plan's bins while it still holds the coordinates).
+// and transform.hip (the fused reprojection can emit the plan's bins while it still holds the coordinates).
 #pragma once
 #include <hip/hip_runtime.h>
 

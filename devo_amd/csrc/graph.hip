@@ -2,7 +2,7 @@
 // :258-265 motionmag, :267-306 keyframe) on the GPU, wave64, gfx950.
 //   * k_motion_partials / k_motion_final: the keyframe motion test.  One pass over ALL edges, no compaction: an edge selects itself by
 //     (ii == i & jj == j) or the reverse and evaluates pops.flow_mag on its P x P pixels (the arithmetic of the fused transform,
-//     ba.hip k_transform: quaternions renormalised on load, Z clamped at 0.1 in proj, identity rotation for `tonly`).  Sums and counts
+//     transform.hip k_transform: quaternions renormalised on load, Z clamped at 0.1 in proj, identity rotation for `tonly`).  Sums and counts
 //     per direction: shuffle wave sums, one fp32 partial per workgroup, the partials added in fp64 in a fixed order by one workgroup.
 //     No float atomics: the means are reproducible from run to run.  A direction without an edge yields 0 / 0 = NaN.
 //   * k_compact_count / k_compact_scatter: a STABLE stream compaction of ii, jj, kk and the rows of net.  The keyframe decision

@@ -2,6 +2,9 @@
 (cuda_ba.graph_tables) serve the BA through ONE launch (devo_ba_import_tables) instead of a second preparation (nine launches at the
 steady-state graph's 45 312 edges).  Everything here is an equality of bits with the BA that prepares its own tables, and the ways the
 shortcut must NOT be taken."""
+import os
+import subprocess
+import sys
 import pytest
 import torch
 from devo_amd import synth
@@ -128,3 +131,60 @@ def test_the_update_operator_offers_its_tables():
         upd(net, inp, corr, None, ii, jj, kk)
     got = _ba(sc)
     assert cuda_ba.import_stats() == n0 + 1 and torch.equal(ref[0], got[0]) and torch.equal(ref[1], got[1])
+
+
+# 4 source frames x 80 patches, every patch seen by 4 target frames: 16 frame-pair groups of 80 edges (n_seg * 64 <= E: the stages count and
+# scatter them through the LDS histogram) and 320 patch groups of 4 (device atomics); patch 7 carries 70 more edges, so k_neighbors_seg meets a
+# group of more than 64.  Shuffled: nothing is grouped beforehand.
+_DUAL_AB = r"""
+import sys, torch
+sys.path.insert(0, sys.argv[1])
+from devo_amd import _lib as L
+from devo_amd.backends import cuda_ba
+patch = torch.arange(320).repeat_interleave(4)
+jj = 4 + torch.arange(4).repeat(320)
+patch = torch.cat([patch, torch.full((70,), 7)])
+jj = torch.cat([jj, 4 + torch.arange(70) % 4])
+order = torch.randperm(patch.numel(), generator=torch.Generator().manual_seed(3))
+kk, jj = patch[order].cuda(), jj[order].cuda()
+ii = kk // 80
+E, bound = kk.numel(), 1 << 20
+nbytes = int(L.lib().devo_ba_workspace_bytes(E, bound, 0))
+ws = torch.empty(2, nbytes, dtype=torch.uint8, device="cuda")
+nb = torch.empty(2, E, dtype=torch.int64, device="cuda")
+key = torch.empty(E + 2, dtype=torch.int64, device="cuda")
+L.check(L.lib().devo_upd_graph_tables(L.ptr(ii), L.ptr(jj), L.ptr(kk), E, bound, L.ptr(ws[0]), nbytes, L.ptr(ws[1]), nbytes, L.ptr(key), L.ptr(nb[0]),
+                                      L.ptr(nb[1]), L.stream()), "graph_tables")
+out = {"key": key[:E].cpu(), "ix": nb[0].cpu(), "jx": nb[1].cpu()}
+for name, w in (("patch", ws[0]), ("pair", ws[1])):
+    n, kx, seg, perm = cuda_ba.prepared_tables(w, E, bound, 0)
+    out[name] = (n, kx.cpu(), seg.cpu(), perm.cpu())
+torch.save(out, sys.argv[2])
+"""
+
+
+def test_both_lists_in_the_same_launches_build_the_tables_of_two_preparations(tmp_path):
+    """devo_upd_graph_tables beyond the single-workgroup size (DEVO_BA_PREP_MULTI_FROM=1 forces it here): both edge lists through the multi-kernel
+    stages together (two problems per launch) against DEVO_UPD_TABLES_DUAL=0, two preparations of one problem each, on the same ii / jj / kk —
+    the same group counts, unique ids, segment starts and grouped edges in both workspaces, the same pair key and neighbours, bit for bit."""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = []
+    for dual in (True, False):
+        env = dict(os.environ)
+        env["DEVO_BA_PREP_MULTI_FROM"] = "1"
+        env.pop("DEVO_UPD_TABLES_DUAL", None)
+        if not dual:
+            env["DEVO_UPD_TABLES_DUAL"] = "0"
+        path = str(tmp_path / f"dual_{int(dual)}.pt")
+        r = subprocess.run([sys.executable, "-c", _DUAL_AB, root, path], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        res.append(torch.load(path))
+    a, b = res
+    assert a["patch"][0] == 320 and a["pair"][0] == 16                # (the graph is the one described above)
+    for name in ("patch", "pair"):
+        assert a[name][0] == b[name][0], name
+        for x, y in zip(a[name][1:], b[name][1:]):
+            assert torch.equal(x, y), name
+    for name in ("key", "ix", "jx"):
+        assert torch.equal(a[name], b[name]), name
+    assert int((a["ix"] >= 0).sum()) == a["ix"].numel() - 320         # every patch has one first and one last edge
