@@ -687,6 +687,67 @@ void pg_shift_frames(TensorList tensors, int64_t k, int64_t n) {
   check(devo_graph_shift_frames(ptrs.data(), rows.data(), (int)ptrs.size(), (int)k, (int)n, stream_of(tensors[0])), "patch_graph.shift_frames");
 }
 
+// ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
+// Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
+// shapes, owns the log and the workspace and reads the status.
+void fr_begin(Tensor poses, Tensor patches, Tensor intrinsics, Tensor tstamps, int64_t M, int64_t n, Tensor new_patches, Tensor new_intrinsics, int64_t counter, double res,
+              int64_t motion_model, double damping, const c10::optional<Tensor>& depth) {
+  pg_geometry("frames.begin_frame", poses, patches, intrinsics);
+  pg_geometry("frames.begin_frame", new_patches, new_patches, new_intrinsics);
+  pg_check_idx("frames.begin_frame", tstamps);
+  const bool has = depth.has_value() && depth->defined();
+  TORCH_CHECK(!has || (depth->is_cuda() && depth->scalar_type() == at::kFloat && depth->is_contiguous()), "frames.begin_frame: depth must be a contiguous float32 tensor on the GPU");
+  c10::DeviceGuard guard(poses.device());
+  check(devo_frame_begin(poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(), tstamps.data_ptr<int64_t>(), (int)(poses.numel() / 7), (int)M,
+                         (int)patches.size(-1), (int)n, new_patches.data_ptr<float>(), new_intrinsics.data_ptr<float>(), counter, (float)res, (int)motion_model, (float)damping,
+                         has ? depth->data_ptr<float>() : nullptr, stream_of(poses)), "frames.begin_frame");
+}
+
+void fr_point_cloud(Tensor poses, Tensor patches, Tensor intrinsics, Tensor ix, int64_t M, int64_t m, int64_t start_frame, Tensor out) {
+  pg_geometry("frames.point_cloud", poses, patches, intrinsics);
+  pg_check_idx("frames.point_cloud", ix);
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= 3 * m, "frames.point_cloud: out must be a contiguous float32 tensor of at least m rows");
+  c10::DeviceGuard guard(poses.device());
+  const int64_t P = patches.size(-1);
+  check(devo_frame_point_cloud(poses.data_ptr<float>(), patches.data_ptr<float>(), intrinsics.data_ptr<float>(), i64p(ix), (int)(poses.numel() / 7),
+                               (int)(patches.numel() / (3 * P * P)), ix.numel(), (int)P, (int)M, (int)m, (int)start_frame, out.data_ptr<float>(), stream_of(poses)),
+        "frames.point_cloud");
+}
+
+void fr_check_log(const char* what, const Tensor& parent, const Tensor& rel, const Tensor& status) {
+  pg_check_idx(what, parent);
+  TORCH_CHECK(rel.is_cuda() && rel.scalar_type() == at::kFloat && rel.is_contiguous() && rel.numel() == 7 * parent.numel(), what, ": rel must be float32 [capacity, 7] on the GPU");
+  TORCH_CHECK(!status.is_cuda() && status.is_pinned() && status.scalar_type() == at::kInt && status.numel() >= 1, what, ": the status word must be a pinned int32 host tensor");
+}
+
+void fr_record_removed(Tensor poses, Tensor tstamps, int64_t k, Tensor parent, Tensor rel, Tensor status) {
+  pg_geometry("frames.record_removed", poses, poses, poses);
+  pg_check_idx("frames.record_removed", tstamps);
+  fr_check_log("frames.record_removed", parent, rel, status);
+  c10::DeviceGuard guard(parent.device());
+  check(devo_frame_record_removed(poses.data_ptr<float>(), i64p(tstamps), (int)std::min<int64_t>(poses.numel() / 7, tstamps.numel()), (int)k, parent.data_ptr<int64_t>(),
+                                  rel.data_ptr<float>(), (int)parent.numel(), status.data_ptr<int>(), stream_of(parent)), "frames.record_removed");
+}
+
+void fr_record_skipped(int64_t t, int64_t t0, Tensor parent, Tensor rel, Tensor status) {
+  fr_check_log("frames.record_skipped", parent, rel, status);
+  c10::DeviceGuard guard(parent.device());
+  check(devo_frame_record_skipped(t, t0, parent.data_ptr<int64_t>(), rel.data_ptr<float>(), (int)parent.numel(), status.data_ptr<int>(), stream_of(parent)),
+        "frames.record_skipped");
+}
+
+void fr_complete(Tensor poses, Tensor tstamps, int64_t n, int64_t counter, Tensor parent, Tensor rel, Tensor out, Tensor ws, Tensor status) {
+  pg_geometry("frames.complete", poses, poses, poses);
+  pg_check_idx("frames.complete", tstamps);
+  fr_check_log("frames.complete", parent, rel, status);
+  TORCH_CHECK(n <= poses.numel() / 7 && n <= tstamps.numel(), "frames.complete: n exceeds the frame buffers");
+  TORCH_CHECK(out.is_cuda() && out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= 7 * counter && ws.is_cuda() && ws.is_contiguous(),
+              "frames.complete: out must be float32 [counter, 7] on the GPU");
+  c10::DeviceGuard guard(parent.device());
+  check(devo_frame_complete(poses.data_ptr<float>(), i64p(tstamps), (int)n, (int)counter, i64p(parent), rel.data_ptr<float>(), (int)parent.numel(), out.data_ptr<float>(),
+                            ws.data_ptr(), (size_t)(ws.numel() * ws.element_size()), status.data_ptr<int>(), stream_of(parent)), "frames.complete");
+}
+
 // ------------------------------------------------------------------------------------------------ training loss (devo_amd/losses.py; csrc/loss.hip)
 // Thin forms of devo_loss_forward / devo_loss_backward: the outputs and the state are allocated here, nothing else happens on the host.
 void loss_check(const char* what, const Tensor& t, at::ScalarType dt) {
@@ -853,6 +914,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   pg.def("append", &pg_append);
   pg.def("shift_frames", &pg_shift_frames);
   pg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_graph_workspace_bytes((int)capacity); });
+  auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
+  fr.def("begin_frame", &fr_begin);
+  fr.def("point_cloud", &fr_point_cloud);
+  fr.def("record_removed", &fr_record_removed);
+  fr.def("record_skipped", &fr_record_skipped);
+  fr.def("complete", &fr_complete);
+  fr.def("complete_workspace_bytes", [](int64_t counter) { return (int64_t)devo_frame_complete_workspace_bytes((int)counter); });
+  fr.def("complete_launches", [](int64_t counter) { return (int64_t)devo_frame_complete_launches((int)counter); });
   auto losses = m.def_submodule("losses", "devo_amd.losses: train.py:172-236, :254-266");
   losses.def("forward", &loss_forward);
   losses.def("backward", &loss_backward);

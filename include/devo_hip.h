@@ -34,7 +34,9 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                               7: devo_voxel_augment, devo_voxel_augment_workspace_bytes;
                               8: devo_voxel_resample, devo_depth_normalise, devo_depth_normalise_workspace_bytes;
                               9: devo_graph_motion, devo_graph_keyframe, devo_graph_remove, devo_graph_append, devo_graph_shift_frames, devo_graph_workspace_bytes
-                                 (devo_loss_state_bytes, devo_loss_forward, devo_loss_backward joined version 9: new symbols, no argument list changed);
+                                 (devo_loss_state_bytes, devo_loss_forward, devo_loss_backward joined version 9: new symbols, no argument list changed;
+                                  so did devo_frame_begin, devo_frame_point_cloud, devo_frame_record_removed, devo_frame_record_skipped,
+                                  devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -709,6 +711,52 @@ int devo_graph_append(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old
  * is `tensors[s]` (HOST array of device pointers), contiguous, with rows of row_bytes[s] (HOST array) bytes; rows k + 1 .. n - 1 of
  * each move down by one (row r <- row r + 1 for r = k .. n - 2, in place). */
 int devo_graph_shift_frames(void* const* tensors, const int64_t* row_bytes, int count, int k, int n, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The per-frame state of DEVO's inference between the update step, the Patchifier and the patch graph: the frame store with the
+ * motion model and the depth initialisation (devo/devo.py:487-488, :502-520), the point cloud behind every update (:342-344) and
+ * the relative-pose log with terminate() (:179-196, :276-280, :534).  poses f32 [N, 7], patches f32 [N, M, 3, P, P], intrinsics
+ * f32 [N, 4], tstamps i64 [N]: the caller's frame buffers (devo.py:56-65).  `status` is a HOST-VISIBLE i32 (pinned host memory,
+ * device-addressable at its own address): 0, or the DEVO_FRAME_STATUS_* code of the last error a kernel met; the caller clears it.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_FRAME_MEDIAN_MAX 32768      /* depth values the median of devo_frame_begin selects from: 3 M P P */
+enum { DEVO_FRAME_COPY_LAST = 0, DEVO_FRAME_DAMPED_LINEAR = 1 };
+enum { DEVO_FRAME_STATUS_BAD_ENTRY = 1,  /* a log entry whose frame lies outside the capacity or whose parent is not an earlier frame */
+       DEVO_FRAME_STATUS_MISSING = 2,    /* a frame below `counter` that is no keyframe and that no chain of entries ties to one */
+       DEVO_FRAME_STATUS_UNSORTED = 3 }; /* tstamps[:n] is not strictly increasing */
+
+/* Row n of the four buffers, ONE launch; no other row is written.
+ *   poses[n]      n > 1: Exp(damping * Log(P[n-1] P[n-2]^-1)) P[n-1] for DEVO_FRAME_DAMPED_LINEAR, a copy of row n - 1 for
+ *                 DEVO_FRAME_COPY_LAST; n <= 1: untouched (devo.py:502-512).
+ *   patches[n]    channels 0 and 1 from new_patches f32 [M, 3, P, P]; channel 2 = depth[patch] (depth f32 [M]) or, with depth == NULL,
+ *                 the LOWER median of patches[n-3 : n, :, 2] — the value of rank (3 M P P - 1) / 2, what torch.median returns; an exact
+ *                 selection (-0 orders below +0; NaN if there is one).  Needs n >= 3 and 3 M P P <= DEVO_FRAME_MEDIAN_MAX: beyond it
+ *                 DEVO_ERR_UNSUPPORTED is returned and nothing is launched.
+ *   intrinsics[n] new_intrinsics f32 [4] / res, a correctly rounded division;  tstamps[n] = counter. */
+int devo_frame_begin(float* poses, float* patches, float* intrinsics, int64_t* tstamps, int N, int M, int P, int n, const float* new_patches,
+                     const float* new_intrinsics, int64_t counter, float res, int motion_model, float damping, const float* depth,
+                     devo_stream_t stream);
+
+/* out f32 [>= m, 3], rows start_frame * M .. m - 1: the centre pixel (P/2, P/2) of patch k through X = G[ix[k]]^-1 ((x - cx) / fx,
+ * (y - cy) / fy, 1, d), out[k] = X[:3] / X[3] (devo.py:342-344; NaN where ix[k] names no frame).  ONE launch; other rows are not touched. */
+int devo_frame_point_cloud(const float* poses, const float* patches, const float* intrinsics, const int64_t* ix, int n_poses, int n_patches, int64_t ix_len,
+                           int P, int M, int m, int start_frame, float* out, devo_stream_t stream);
+
+/* The log of terminate(): parent i64 [capacity] (-1: no entry), rel f32 [capacity, 7].
+ * record_removed (devo.py:276-280, BEFORE the frame buffers shift): t0 = tstamps[k-1], t1 = tstamps[k] read on the device,
+ * parent[t1] = t0, rel[t1] = P[k] P[k-1]^-1.  record_skipped (devo.py:534): parent[t] = t0, rel[t] = identity.  One launch each. */
+int devo_frame_record_removed(const float* poses, const int64_t* tstamps, int n_poses, int k, int64_t* parent, float* rel, int capacity, int* status,
+                              devo_stream_t stream);
+int devo_frame_record_skipped(int64_t t, int64_t t0, int64_t* parent, float* rel, int capacity, int* status, devo_stream_t stream);
+
+/* terminate() (devo.py:186-196): out f32 [counter, 7] = the INVERSE of pose(t), pose(tstamps[i]) = poses[i] for i < n (a keyframe wins
+ * over a log entry; tstamps[:n] strictly increasing, as the state machine keeps it), pose(t) = rel[t] pose(parent[t]) otherwise.
+ * Parallel pointer jumping, 1 + ceil(log2(counter)) launches (devo_frame_complete_launches), no bound on the depth of a chain.
+ * ws: devo_frame_complete_workspace_bytes(counter).  counter > capacity: DEVO_ERR_ARG. */
+size_t devo_frame_complete_workspace_bytes(int counter);
+int devo_frame_complete_launches(int counter);
+int devo_frame_complete(const float* poses, const int64_t* tstamps, int n, int counter, const int64_t* parent, const float* rel, int capacity, float* out,
+                        void* ws, size_t ws_bytes, int* status, devo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The training loss of one update iteration (train.py:172-236 and the metrics of :254-266); T = fp32 or fp64 throughout.
