@@ -687,6 +687,48 @@ void pg_shift_frames(TensorList tensors, int64_t k, int64_t n) {
   check(devo_graph_shift_frames(ptrs.data(), rows.data(), (int)ptrs.size(), (int)k, (int)n, stream_of(tensors[0])), "patch_graph.shift_frames");
 }
 
+// ------------------------------------------------------------------------------------------------ training graph (devo_amd/train_graph.py; csrc/train_graph.hip)
+// Thin forms of the devo_train_graph_* entry points.  idx: int64 [3, cap] (ii, jj, kk); close / far: int64 [4, cap] (position, ii, jj, kk).  The Python
+// class owns the buffers, the size model and the version counters.
+void tg_check_rows(const char* what, const Tensor& t, int64_t rows) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kLong && t.is_contiguous() && t.dim() == 2 && t.size(0) == rows, what, ": expected a contiguous int64 [", rows, ", cap] tensor on the GPU");
+}
+void tg_init(Tensor idx, int64_t M, int64_t init_frames, Tensor close, Tensor far_, Tensor ws) {
+  tg_check_rows("train_graph.init", idx, 3); tg_check_rows("train_graph.init", close, 4); tg_check_rows("train_graph.init", far_, 4);
+  require_gpu(ws);
+  c10::DeviceGuard guard(idx.device());
+  check(devo_train_graph_init(idx.data_ptr<int64_t>(), idx.size(1), (int)M, (int)init_frames, close.data_ptr<int64_t>(), close.size(1), far_.data_ptr<int64_t>(), far_.size(1),
+                              ws.data_ptr(), (size_t)ws.numel(), stream_of(idx)), "train_graph.init");
+}
+void tg_grow(Tensor src, int64_t E_old, Tensor dst, int64_t E_new, int64_t M, int64_t n, bool drop, Tensor net_old, Tensor net_new, const c10::optional<Tensor>& map,
+             Tensor poses_in, Tensor poses_out, Tensor patches_in, Tensor patches_out, Tensor close, Tensor far_, Tensor ws) {
+  tg_check_rows("train_graph.grow", src, 3); tg_check_rows("train_graph.grow", dst, 3); tg_check_rows("train_graph.grow", close, 4); tg_check_rows("train_graph.grow", far_, 4);
+  pg_geometry("train_graph.grow", poses_in, patches_in, poses_out);
+  pg_geometry("train_graph.grow", poses_out, patches_out, poses_out);
+  require_gpu(net_old, net_new, ws);
+  TORCH_CHECK(net_old.is_contiguous() && net_new.is_contiguous() && net_old.scalar_type() == net_new.scalar_type() && net_old.size(-1) == net_new.size(-1) &&
+              net_old.numel() == E_old * net_old.size(-1) && net_new.numel() == E_new * net_new.size(-1), "train_graph.grow: net [E_old, dim] and net' [E_new, dim], contiguous, one dtype");
+  TORCH_CHECK(poses_out.numel() == poses_in.numel() && patches_out.numel() == patches_in.numel() && patches_in.dim() >= 3, "train_graph.grow: poses' and patches' have the shapes of poses and patches");
+  const bool has = map.has_value() && map->defined();
+  TORCH_CHECK(!has || (map->is_cuda() && map->scalar_type() == at::kInt && map->is_contiguous() && map->numel() >= E_old), "train_graph.grow: map must be a contiguous int32 tensor of E_old entries on the GPU");
+  c10::DeviceGuard guard(src.device());
+  const int64_t P = patches_in.size(-1), N = poses_in.numel() / 7;
+  TORCH_CHECK(patches_in.numel() == N * M * 3 * P * P, "train_graph.grow: patches must hold M patches for each of the ", N, " poses");
+  check(devo_train_graph_grow(i64p(src), src.size(1), (int)E_old, dst.data_ptr<int64_t>(), dst.size(1), (int)E_new, (int)M, (int)n, drop ? 1 : 0, net_old.data_ptr(),
+                              net_new.data_ptr(), (int)net_new.size(-1), dtype_code(net_new), has ? map->data_ptr<int>() : nullptr, poses_in.data_ptr<float>(),
+                              poses_out.data_ptr<float>(), (int)N, patches_in.data_ptr<float>(), patches_out.data_ptr<float>(), (int)P, close.data_ptr<int64_t>(),
+                              close.size(1), far_.data_ptr<int64_t>(), far_.size(1), ws.data_ptr(), (size_t)ws.numel(), stream_of(src)), "train_graph.grow");
+}
+void tg_net_backward(Tensor grad_new, Tensor map, Tensor grad_old, int64_t E_new) {
+  require_gpu(grad_new, map, grad_old);
+  TORCH_CHECK(grad_new.is_contiguous() && grad_old.is_contiguous() && grad_new.scalar_type() == grad_old.scalar_type() && grad_new.size(-1) == grad_old.size(-1) &&
+              grad_new.numel() == E_new * grad_new.size(-1), "train_graph.net_backward: contiguous gradients of one dtype and row length");
+  TORCH_CHECK(map.scalar_type() == at::kInt && map.is_contiguous() && map.numel() * grad_old.size(-1) == grad_old.numel(), "train_graph.net_backward: map must be a contiguous int32 tensor of E_old entries");
+  c10::DeviceGuard guard(map.device());
+  check(devo_train_graph_net_backward(grad_new.data_ptr(), map.data_ptr<int>(), grad_old.data_ptr(), (int)map.numel(), (int)E_new, (int)grad_old.size(-1), dtype_code(grad_old),
+                                      stream_of(map)), "train_graph.net_backward");
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -914,6 +956,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   pg.def("append", &pg_append);
   pg.def("shift_frames", &pg_shift_frames);
   pg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_graph_workspace_bytes((int)capacity); });
+  auto tg = m.def_submodule("train_graph", "devo_amd.train_graph: devo/enet.py:297-339, :359-369 on the graph");
+  tg.def("init", &tg_init);
+  tg.def("grow", &tg_grow);
+  tg.def("net_backward", &tg_net_backward);
+  tg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_train_graph_workspace_bytes((int)capacity); });
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

@@ -71,13 +71,22 @@ class TrainNet(nn.Module):
 
     OBJECTIVES = ("bench", "reference")
 
-    def forward(self, batch, iters=18, corr_dropout=0.2, flow_weight=0.1, pose_weight=10.0, objective="bench"):
+    SCHEDULES = ("full", "reference")
+
+    def forward(self, batch, iters=18, corr_dropout=0.2, flow_weight=0.1, pose_weight=10.0, objective="bench", schedule="full", init_frames=None, warmup=8):
         """One sequence (batch 1) through `iters` update iterations on its patch graph -> scalar loss
-        (enet.py:300-370 on a fixed full graph + train.py:172-236).  objective: "bench", the simplified composition below (what
+        (enet.py:300-370 + train.py:172-236).  objective: "bench", the simplified composition below (what
         bench.py --mode train measures), or "reference", the reference's loss through devo_amd.losses (scale-aligned pose term, the
-        scorer term in the last iteration, train.py's default scores weight)."""
+        scorer term in the last iteration, train.py's default scores weight).  schedule: "full", every iteration on the batch's fixed
+        full graph, or "reference", the reference's growing graph (enet.py:297-339) driven by devo_amd.train_graph.TrainGraph: the
+        batch's ii / jj / kk are ignored, the graph starts on init_frames (default min(8, n)) frames and grows by one frame per
+        iteration from iteration `warmup` on."""
         if objective not in self.OBJECTIVES:
             raise ValueError(f"objective {objective!r}: one of {self.OBJECTIVES}")
+        if schedule not in self.SCHEDULES:
+            raise ValueError(f"schedule {schedule!r}: one of {self.SCHEDULES}")
+        if schedule == "reference" and "wiring_check" not in batch:
+            return self._forward_growing(batch, iters, corr_dropout, flow_weight, pose_weight, objective, init_frames, warmup)
         if "wiring_check" in batch:
             # not a training step: sum(parameters) * factor, so that a CPU / gloo run can check the DDP wiring of THIS module
             # (every parameter in the all-reduced bucket) without the HIP kernels — tests/test_distributed_gloo.py
@@ -154,6 +163,81 @@ class TrainNet(nn.Module):
             return loss
         return loss + 1e-3 * scores.mean()                      # (the reference's scorer term, train.py:226-232, reduced to a mean)
 
+    def _forward_growing(self, b, iters, corr_dropout, flow_weight, pose_weight, objective, init_frames, warmup):
+        """forward() under schedule="reference": enet.py:297-370.  The graph is `g`'s in every iteration: a growth (g.step) prepends the
+        new frame's edges, extends net with zero rows (gradient flows through), copies the previous pose and takes the depth median; the
+        drop is drawn here, only inside a growth (the reference's draw order, enet.py:331).  The flow term runs on g.close, the pose term
+        on the g.n frames of the graph, the scorer term (last iteration) on g.far.  The per-iteration body (lookup, operator, two BA
+        steps, the two objectives) is forward()'s, written out a second time so that the "full" path keeps its exact sequence of calls:
+        a change to one of the two loops belongs in the other as well."""
+        from . import altcorr, projective_ops as pops
+        from .ba import BA
+        from .lietorch import SE3
+        n, M = b["poses_gt"].shape[1], b["M"]
+        dev = b["poses_gt"].device
+        from . import train_graph
+        g = train_graph.TrainGraph(n, M, P=self.P, dim=self.dim, init_frames=min(8, n) if init_frames is None else init_frames, warmup=warmup, device=dev)
+        fmap, gmap, imap, _, _, scores = self.patchify(self.normalise_images(b["images"]), M, coords=b["centres"])
+        pyramid = [altcorr.channels_last(fmap), altcorr.channels_last(torch.nn.functional.avg_pool2d(fmap[0], 4, 4)[None])]   # enet.py:207-210
+        imap = imap.view(1, -1, self.dim)
+        Ps = SE3(b["poses_gt"])
+        poses = b["poses0"].clone()
+        patches = b["patches0"].clone()
+        net = torch.zeros(1, len(g), self.dim, device=dev)
+        bounds = [-64, -64, b["W"] + 64, b["H"] + 64]
+        if objective == "reference":
+            from . import losses
+        loss = 0.0
+        for it in range(iters):
+            poses, patches = poses.detach(), patches.detach()
+            if g.grows(it):                                           # enet.py:319-339
+                net, poses, patches = g.step(it, net, poses, patches, drop=np.random.rand() < 0.1)
+            Gs = SE3(poses)
+            ii, jj, kk, close = g.ii, g.jj, g.kk, g.close
+            E, nf = ii.numel(), g.n
+            coords = pops.transform(Gs, patches, b["intr"], ii, jj, kk)
+            coords1 = coords.permute(0, 1, 4, 2, 3).contiguous()
+            if FUSED_LOOKUP:
+                corr = altcorr.corr_pyramid(gmap, pyramid, coords1, kk, jj, b["R"], (1, 4), dropout=corr_dropout)
+            else:
+                corr = torch.stack([altcorr.corr(gmap, pyramid[0], coords1 / 1, kk, jj, b["R"], corr_dropout),
+                                    altcorr.corr(gmap, pyramid[1], coords1 / 4, kk, jj, b["R"], corr_dropout)], -1).view(1, E, -1)
+            net, (delta, weight, _) = self.update(net, torch.index_select(imap, 1, kk), corr, None, ii, jj, kk)
+            target = coords[..., self.P // 2, self.P // 2, :] + delta
+            for _ in range(2):
+                Gs, patches = BA(Gs, patches, b["intr"], target, weight, 1e-4, ii, jj, kk, bounds, ep=10.0, fixedp=1, n_frames=nf)
+            poses = Gs.data
+            with torch.no_grad():                                      # enet.py:366: the truth on the CURRENT close edges
+                coords_gt, valid_gt = pops.transform(Ps, b["patches_gt"], b["intr"], close.ii, close.jj, close.kk, valid=True)[:2]
+            cf = pops.transform(Gs, patches, b["intr"], close.ii, close.jj, close.kk)
+            Gn, Pn = SE3(Gs.data[:, :nf]), SE3(Ps.data[:, :nf])        # enet.py:369: Gs[:, :n], Ps[:, :n]
+            if objective == "reference":                               # enet.py:362-369 + train.py:176-236
+                scorer = None
+                if it == iters - 1:
+                    far = g.far
+                    with torch.no_grad():
+                        coords_far = pops.transform(Gs, patches, b["intr"], far.ii, far.jj, far.kk)
+                        coords_gt_far, valid_far = pops.transform(Ps, b["patches_gt"], b["intr"], far.ii, far.jj, far.kk, valid=True)[:2]
+                    scorer = (scores, valid_far[0], coords_far[0], coords_gt_far[0], torch.index_select(weight.detach()[0], 0, far.pos), far.kk)
+                loss = loss + losses.iteration_loss(valid_gt, cf, coords_gt, Gn, Pn, index=it, flow_weight=flow_weight, pose_weight=pose_weight, scorer=scorer)[0]
+                continue
+            e = (cf - coords_gt).norm(dim=-1).reshape(-1, self.P * self.P)
+            ok = valid_gt.reshape(-1) > 0.5
+            flow_loss = (e.min(dim=-1).values * ok).sum() / ok.sum().clamp(min=1)
+            q = torch.arange(nf * (nf - 1), device=dev)               # the ordered frame pairs fi != fj in closed form (no mask gather)
+            fi, r = q // (nf - 1), q % (nf - 1)
+            fj = r + (r >= fi)
+            P1, P2 = Gn.inv(), Pn.inv()
+            take = lambda G, idx: SE3(torch.index_select(G.data, 1, idx))
+            e1 = ((take(P1, fi).inv() * take(P1, fj)) * (take(P2, fi).inv() * take(P2, fj)).inv()).log()
+            pose_loss = e1[..., 0:3].norm(dim=-1).mean() + e1[..., 3:6].norm(dim=-1).mean()
+            loss = loss + flow_weight * flow_loss
+            if it >= 2:
+                loss = loss + pose_weight * pose_loss
+        if objective == "reference":
+            return loss
+        return loss + 1e-3 * scores.mean()
+
 
 def make_batch(workload="cfg2_m80", seed=1234, device="cuda"):
     """One synthetic training sequence: features, patches with perturbed depths, identity-initialised poses,
@@ -194,10 +278,11 @@ def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", ra
     return net, model, opt
 
 
-def train_step(model, opt, batch, iters=18, clip=10.0, objective="bench"):
-    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step (train.py:166-250).  objective: TrainNet.forward's."""
+def train_step(model, opt, batch, iters=18, clip=10.0, objective="bench", schedule="full", **schedule_args):
+    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step (train.py:166-250).  objective, schedule
+    (and init_frames / warmup through schedule_args): TrainNet.forward's."""
     opt.zero_grad(set_to_none=True)
-    loss = model(batch, iters=iters, objective=objective)
+    loss = model(batch, iters=iters, objective=objective, schedule=schedule, **schedule_args)
     loss.backward()
     torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
     opt.step()

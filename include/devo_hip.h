@@ -36,7 +36,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                               9: devo_graph_motion, devo_graph_keyframe, devo_graph_remove, devo_graph_append, devo_graph_shift_frames, devo_graph_workspace_bytes
                                  (devo_loss_state_bytes, devo_loss_forward, devo_loss_backward joined version 9: new symbols, no argument list changed;
                                   so did devo_frame_begin, devo_frame_point_cloud, devo_frame_record_removed, devo_frame_record_skipped,
-                                  devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches);
+                                  devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
+                                  devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -787,6 +788,33 @@ int devo_loss_forward(const void* x, const void* y, const void* v, int Ec, int P
  * in the first six), g_scores T [n_patches]; each may be NULL. */
 int devo_loss_backward(const void* g, const void* state, size_t state_bytes, int Ec, int P, int n, int Ef, int n_patches, double flow_weight, double pose_weight,
                        double scores_weight, void* g_coords, void* g_Gs, void* g_scores, int dtype, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The growing patch graph of the training loop (devo/enet.py:297-339 and the edge selections of :359-369; csrc/train_graph.hip;
+ * devo_amd/train_graph.py).  Patches are frame-major, M per frame.  An index buffer holds three rows of `cap` int64 each (ii, jj, kk),
+ * a list buffer four (position in the edge list, ii, jj, kk): close = the edges with 0 < |ii - jj| <= 2, far = those with <= 16, in
+ * edge order.  Every total is host arithmetic (the caller passes E_new); every store is guarded by its buffer's capacity.
+ * ws: devo_train_graph_workspace_bytes(capacity in edges).  Nothing waits for the device.
+ *   init   the graph flatmeshgrid(where(ix < init_frames), arange(init_frames)) in closed form and its lists.  2 launches.
+ *   grow   the growth to frame n (1 <= n < N <= DEVO_TRAIN_GRAPH_MAX_FRAMES): dst = [(p, n) for patches p of frames < n] +
+ *          [(p, j) for patches p of frame n, j in 0..n] + src, then (drop != 0) the stable compaction that keeps ii != n - 4 and
+ *          jj != n - 4; net_new T [E_new, dim] = zero rows for the new edges, the old rows behind them, compacted alike (fp16 / fp32,
+ *          dim a multiple of 8, 16-byte aligned); map i32 [E_old] (needed under a drop, else may be NULL): the new row of an old row
+ *          or -1; poses_out f32 [N, 7] = poses_in with row n = row n - 1; patches_out f32 [N M, 3, P, P] = patches_in with channel 2
+ *          of frame n = the lower median of channel 2 of frames n - 2 and n - 1 (2 M P P <= DEVO_FRAME_MEDIAN_MAX values; NaN if
+ *          there is one); the lists of dst.  Outputs never alias inputs.  3 launches.
+ *   net_backward   grad_old T [E_old, dim] = 0 + grad_new[map] (zero where map < 0; the sum turns -0 into +0, as the torch composition's
+ *          index_put_(accumulate) does).  1 launch.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_TRAIN_GRAPH_MAX_FRAMES 64
+size_t devo_train_graph_workspace_bytes(int capacity);
+int devo_train_graph_init(int64_t* idx, int64_t idx_cap, int M, int init_frames, int64_t* close, int64_t close_cap, int64_t* far_, int64_t far_cap,
+                          void* ws, size_t ws_bytes, devo_stream_t stream);
+int devo_train_graph_grow(const int64_t* src_idx, int64_t src_cap, int E_old, int64_t* dst_idx, int64_t dst_cap, int E_new, int M, int n, int drop,
+                          const void* net_old, void* net_new, int dim, int net_dtype, int* map, const float* poses_in, float* poses_out, int N,
+                          const float* patches_in, float* patches_out, int P, int64_t* close, int64_t close_cap, int64_t* far_, int64_t far_cap, void* ws,
+                          size_t ws_bytes, devo_stream_t stream);
+int devo_train_graph_net_backward(const void* grad_new, const int* map, void* grad_old, int E_old, int E_new, int dim, int net_dtype, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
