@@ -3,6 +3,9 @@ altcorr (patch correlation lookup), fastba (sparse Gauss-Newton BA) and the liet
 HIP kernels behind a C ABI (include/devo_hip.h, devo_amd/lib/libdevo_hip.so) and the reference's own Python
 extension-module interfaces (devo_amd.backends.{cuda_corr, cuda_ba, lietorch_backends}).
 
+The training input path sits beside it: `data` (the sample's tail) and `frame_graph` (a scene's frame graph and the clip sampler
+that walks it).
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """

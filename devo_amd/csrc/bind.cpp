@@ -729,6 +729,55 @@ void tg_net_backward(Tensor grad_new, Tensor map, Tensor grad_old, int64_t E_new
                                       stream_of(map)), "train_graph.net_backward");
 }
 
+// ------------------------------------------------------------------------------------------------ frame graph (devo_amd/frame_graph.py; csrc/frame_graph.hip)
+// The devo_frame_graph_* entry points on tensors: fp32, contiguous, on the GPU; each call owns its workspace (this runs once per scene).
+void fg_check(const char* what, const Tensor& t, int64_t dims) {
+  TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kFloat && t.is_contiguous() && t.dim() == dims, what, ": expected a contiguous float32 tensor of ", dims, " dimensions on the GPU");
+}
+Tensor fg_workspace(const char* what, const Tensor& like, int64_t N, int64_t h, int64_t w) {
+  TORCH_CHECK(N >= 1 && N <= DEVO_FRAME_GRAPH_MAX_FRAMES, what, ": 1 <= N <= ", DEVO_FRAME_GRAPH_MAX_FRAMES, ", got ", N);
+  TORCH_CHECK(h >= 1 && w >= 1 && 2 * h * w < DEVO_FRAME_GRAPH_MAX_POINTS, what, ": maps of ", h, " x ", w, " are not supported: 2 h w must stay below ", DEVO_FRAME_GRAPH_MAX_POINTS);
+  return at::empty({(int64_t)devo_frame_graph_workspace_bytes((int)N, (int)h, (int)w)}, like.options().dtype(at::kByte));
+}
+Tensor fg_disps(Tensor depths) {
+  fg_check("frame_graph.disps", depths, 3);
+  c10::DeviceGuard guard(depths.device());
+  fg_workspace("frame_graph.disps", depths, depths.size(0), depths.size(1), depths.size(2));      // (the size checks)
+  Tensor out = at::empty_like(depths);
+  check(devo_frame_graph_disps(depths.data_ptr<float>(), out.data_ptr<float>(), (int)depths.size(0), (int)depths.size(1), (int)depths.size(2), stream_of(depths)),
+        "frame_graph.disps");
+  return out;
+}
+Tensor fg_distances(Tensor poses, Tensor disps, Tensor intrinsics, double scale) {
+  fg_check("frame_graph.distances", poses, 2); fg_check("frame_graph.distances", disps, 3); fg_check("frame_graph.distances", intrinsics, 2);
+  const int64_t N = disps.size(0);
+  TORCH_CHECK(poses.size(0) == N && poses.size(1) == 7 && intrinsics.size(0) == N && intrinsics.size(1) == 4 && poses.device() == disps.device() &&
+              intrinsics.device() == disps.device(), "frame_graph.distances: poses [N, 7], disps [N, h, w] and intrinsics [N, 4] of one N on one device");
+  c10::DeviceGuard guard(disps.device());
+  Tensor ws = fg_workspace("frame_graph.distances", disps, N, disps.size(1), disps.size(2));
+  Tensor matrix = at::empty({N, N}, disps.options());
+  check(devo_frame_graph_distances(poses.data_ptr<float>(), disps.data_ptr<float>(), intrinsics.data_ptr<float>(), (int)N, (int)disps.size(1), (int)disps.size(2), (float)scale,
+                                   matrix.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(), stream_of(disps)), "frame_graph.distances");
+  return matrix;
+}
+// (rowptr i64 [N + 1], cols i64, dists f32); waits once for the total length
+TensorList fg_lists(Tensor matrix, double max_flow) {
+  fg_check("frame_graph.lists", matrix, 2);
+  const int64_t N = matrix.size(0);
+  TORCH_CHECK(matrix.size(1) == N, "frame_graph.lists: the matrix is square");
+  c10::DeviceGuard guard(matrix.device());
+  Tensor ws = fg_workspace("frame_graph.lists", matrix, N, 1, 1);
+  Tensor rowptr = at::empty({N + 1}, matrix.options().dtype(at::kLong));
+  check(devo_frame_graph_lists(matrix.data_ptr<float>(), (int)N, (float)max_flow, rowptr.data_ptr<int64_t>(), nullptr, nullptr, 0, ws.data_ptr(), (size_t)ws.numel(),
+                               stream_of(matrix)), "frame_graph.lists");
+  const int64_t total = rowptr[N].item<int64_t>();
+  Tensor cols = at::empty({total}, rowptr.options()), dists = at::empty({total}, matrix.options());
+  if (total > 0)
+    check(devo_frame_graph_lists(matrix.data_ptr<float>(), (int)N, (float)max_flow, rowptr.data_ptr<int64_t>(), cols.data_ptr<int64_t>(), dists.data_ptr<float>(), total,
+                                 ws.data_ptr(), (size_t)ws.numel(), stream_of(matrix)), "frame_graph.lists");
+  return {rowptr, cols, dists};
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -883,6 +932,9 @@ TORCH_LIBRARY(devo_hip, m) {
         "bool deterministic, float flow_weight, float pose_weight, float scores_weight, bool use_pose) -> Tensor[]");
   m.def("loss_backward(Tensor g, Tensor state, int Ec, int P, int n, int Ef, int n_patches, float flow_weight, float pose_weight, float scores_weight, bool need_coords, "
         "bool need_Gs, bool need_scores) -> Tensor[]");
+  m.def("frame_graph_disps(Tensor depths) -> Tensor");
+  m.def("frame_graph_distances(Tensor poses, Tensor disps, Tensor intrinsics, float scale) -> Tensor");
+  m.def("frame_graph_lists(Tensor matrix, float max_flow) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -902,6 +954,9 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("se3_act4", &lie_binary<devo_se3_act4, 4>);
   m.impl("loss_forward", &loss_forward);
   m.impl("loss_backward", &loss_backward);
+  m.impl("frame_graph_disps", &fg_disps);
+  m.impl("frame_graph_distances", &fg_distances);
+  m.impl("frame_graph_lists", &fg_lists);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -961,6 +1016,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   tg.def("grow", &tg_grow);
   tg.def("net_backward", &tg_net_backward);
   tg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_train_graph_workspace_bytes((int)capacity); });
+  auto fg = m.def_submodule("frame_graph", "devo_amd.frame_graph: devo/data_readers/base.py:263-286 over rgbd_utils.py:104-141");
+  fg.def("disps", &fg_disps);
+  fg.def("distances", &fg_distances);
+  fg.def("lists", &fg_lists);
+  fg.def("workspace_bytes", [](int64_t N, int64_t h, int64_t w) { return (int64_t)devo_frame_graph_workspace_bytes((int)N, (int)h, (int)w); });
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

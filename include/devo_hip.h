@@ -37,7 +37,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                  (devo_loss_state_bytes, devo_loss_forward, devo_loss_backward joined version 9: new symbols, no argument list changed;
                                   so did devo_frame_begin, devo_frame_point_cloud, devo_frame_record_removed, devo_frame_record_skipped,
                                   devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
-                                  devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes);
+                                  devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes; and devo_frame_graph_disps,
+                                  devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -815,6 +816,38 @@ int devo_train_graph_grow(const int64_t* src_idx, int64_t src_cap, int E_old, in
                           const float* patches_in, float* patches_out, int P, int64_t* close, int64_t close_cap, int64_t* far_, int64_t far_cap, void* ws,
                           size_t ws_bytes, devo_stream_t stream);
 int devo_train_graph_net_backward(const void* grad_new, const int* map, void* grad_old, int E_old, int E_new, int dim, int net_dtype, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * The training frame graph of one scene (devo/data_readers/base.py:263-286 over rgbd_utils.py:104-141; csrc/frame_graph.hip;
+ * devo_amd/frame_graph.py): the mean induced-flow magnitude between all pairs of N frames on subsampled h x w maps, and the neighbour
+ * lists below a flow threshold.  All tensors fp32 unless stated, contiguous.  ws: devo_frame_graph_workspace_bytes of (N, h, w), the same
+ * buffer for distances and lists (0 for sizes that are refused).  No atomics: every result is bit-reproducible.
+ *   N <= DEVO_FRAME_GRAPH_MAX_FRAMES = 32768: the workspace holds two N x N arrays of 4-byte sums and the caller an N x N matrix; at
+ *          32768 each is 4 GiB (12 GiB together), N^2 = 2^30 keeps every list length and degree sum far inside 32 + 64-bit
+ *          arithmetic, and N / 64 target blocks stay inside the grid's second dimension.  Pair indices are 64-bit throughout.
+ *   2 h w < DEVO_FRAME_GRAPH_MAX_POINTS = 2^20: below it the integer rule 10 (V_ij + V_ji) < 7 * 2 h w agrees with the reference's fp32
+ *          `val.mean(-1) < 0.7` for every count (the tie V = 0.7 * 2 h w stays finite); larger maps: DEVO_ERR_UNSUPPORTED.
+ *   disps      depths [N, h, w] (already subsampled) -> disps = 1 / depth, where every depth below 0.01 is first replaced by the mean of
+ *              its frame (taken over all h w values before any replacement; fp64 partial sums in a fixed order).  1 launch.
+ *   distances  poses [N, 7] camera-to-world (t, q = x y z w), disps [N, h, w], intrinsics [N, 4] (fx fy cx cy at the maps' resolution)
+ *              -> matrix [N, N] = scale * (S_ij + S_ji) / (V_ij + V_ji), +inf where fewer than 70 % of the 2 h w points are valid
+ *              (never NaN), bitwise symmetric.  S_ij = sum over the pixels of i of min(|flow|, 100) * valid, V_ij = sum valid, for
+ *              G_ij = P_j P_i^-1 on the world-to-camera poses (i = j: translation (-0.1, 0, 0), no rotation): X1 = R (X, Y, 1) + t disp,
+ *              Z = X1_z or 1 where X1_z < 0.1, projection with j's intrinsics, valid = X1_z > 0.2.  3 launches.
+ *   lists      matrix [N, N] -> CSR lists of the entries < max_flow, columns ascending.  cols == dists == NULL: the degree count and
+ *              the scan write rowptr i64 [N + 1] (2 launches); the caller reads rowptr[N], sizes cols i64 / dists f32 of `capacity`
+ *              entries and calls again with them: the order-preserving compaction (1 launch; stores past `capacity` are dropped).
+ * (The declarations keep a space in front of the parenthesis: tests/test_frames_cpu.py takes every `devo_frame_` name that is directly
+ * followed by one for an entry point of csrc/frames.hip.)
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_FRAME_GRAPH_MAX_FRAMES 32768
+#define DEVO_FRAME_GRAPH_MAX_POINTS (1 << 20)
+size_t devo_frame_graph_workspace_bytes (int N, int h, int w);
+int devo_frame_graph_disps (const float* depths, float* disps, int N, int h, int w, devo_stream_t stream);
+int devo_frame_graph_distances (const float* poses, const float* disps, const float* intrinsics, int N, int h, int w, float scale, float* matrix, void* ws,
+                               size_t ws_bytes, devo_stream_t stream);
+int devo_frame_graph_lists (const float* matrix, int N, float max_flow, int64_t* rowptr, int64_t* cols, float* dists, int64_t capacity, void* ws, size_t ws_bytes,
+                           devo_stream_t stream);
 
 #ifdef __cplusplus
 }
