@@ -6,6 +6,8 @@ extension-module interfaces (devo_amd.backends.{cuda_corr, cuda_ba, lietorch_bac
 The training input path sits beside it: `data` (the sample's tail) and `frame_graph` (a scene's frame graph and the clip sampler
 that walks it).
 
+`select` is the per-frame patch selection (the reference's PatchSelector and the Patchifier's tail behind it) as one launch.
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """

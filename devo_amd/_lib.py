@@ -162,6 +162,10 @@ _SIGNATURES.update({
     "devo_frame_graph_distances": [_vp, _vp, _vp, _i, _i, _i, _f, _vp, _vp, _sz, _vp],
     "devo_frame_graph_lists": [_vp, _i, _f, _vp, _vp, _vp, _i64, _vp, _sz, _vp],
 })
+_SIGNATURES.update({
+    "devo_patch_select": [_vp, _i64, _i64, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _i64, _i64, _i64, _i, _i, _i,
+                          _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+})
 for _n in ("exp", "log", "inv"):
     _SIGNATURES[f"devo_se3_{_n}"] = [_vp, _vp, _i64, _i, _vp]
     _SIGNATURES[f"devo_se3_{_n}_backward"] = [_vp, _vp, _vp, _i64, _i, _vp]

@@ -778,6 +778,46 @@ TensorList fg_lists(Tensor matrix, double max_flow) {
   return {rowptr, cols, dists};
 }
 
+// ------------------------------------------------------------------------------------------------ patch selection (devo_amd/select.py; csrc/select.hip)
+// devo_patch_select on tensors: scores f32 [n, h, w] (any strides), the outputs are allocated here.  The Python module checks modes and sizes, draws
+// the noise / candidates and reads the nms counts.  -> {x, y, xy, scores, patches, index, counts (nms; empty otherwise)}
+TensorList patch_select(const Tensor& scores, int64_t m, int64_t mode, bool grid, int64_t k, bool pad, const c10::optional<Tensor>& noise,
+                        const c10::optional<Tensor>& cand_x, const c10::optional<Tensor>& cand_y, int64_t offset, bool clamp, int64_t cx0, int64_t cx1, int64_t cy0,
+                        int64_t cy1, const c10::optional<Tensor>& disps, int64_t P) {
+  TORCH_CHECK(scores.is_cuda() && scores.scalar_type() == at::kFloat && scores.dim() == 3, "select: scores must be a float32 tensor [n, h, w] on the GPU");
+  const int64_t n = scores.size(0), h = scores.size(1), w = scores.size(2);
+  TORCH_CHECK(n >= 1 && h >= 1 && w >= 1 && m >= 1 && m <= DEVO_SELECT_MAX_CELLS && P >= 1, "select: n, h, w, P >= 1 and 1 <= m <= ", DEVO_SELECT_MAX_CELLS);
+  const int64_t f = grid ? 2 * k : k;
+  TORCH_CHECK(k >= 1, "select: k >= 1");
+  const int64_t C = pad ? ((h + (f - h % f) % f) / k) * ((w + (f - w % f) % f) / k) : (h / k) * (w / k);
+  const bool has_noise = noise.has_value() && noise->defined(), has_cand = cand_x.has_value() && cand_x->defined() && cand_y.has_value() && cand_y->defined();
+  const bool has_disps = disps.has_value() && disps->defined();
+  if (mode == DEVO_SELECT_MULTI)
+    TORCH_CHECK(has_noise && noise->is_cuda() && noise->scalar_type() == at::kFloat && noise->is_contiguous() && noise->dim() == 2 && noise->size(0) == n &&
+                noise->size(1) == C + 16 * m && noise->device() == scores.device(), "select: multi takes noise float32 [n, C + 16 m] = [", n, ", ", C + 16 * m, "] on the scores' device");
+  if (mode == DEVO_SELECT_3XRANDOM) {
+    TORCH_CHECK(has_cand, "select: 3xrandom takes candidates (x, y)");
+    for (const Tensor* t : {&*cand_x, &*cand_y})
+      TORCH_CHECK(t->is_cuda() && t->scalar_type() == at::kLong && t->is_contiguous() && t->dim() == 2 && t->size(0) == n && t->size(1) == 3 * m && t->device() == scores.device(),
+                  "select: candidates must be contiguous int64 tensors [n, 3 m] on the scores' device");
+  }
+  if (has_disps)
+    TORCH_CHECK(disps->is_cuda() && disps->scalar_type() == at::kFloat && disps->dim() == 3 && disps->size(0) == n && disps->device() == scores.device(),
+                "select: disps must be a float32 tensor [n, H, W] on the scores' device");
+  c10::DeviceGuard guard(scores.device());
+  const auto fo = scores.options().memory_format(c10::nullopt), lo = fo.dtype(at::kLong);
+  Tensor x = at::empty({n, m}, lo), y = at::empty({n, m}, lo), index = at::empty({n * m}, lo), xy = at::empty({n, m, 2}, fo), sc = at::empty({n, m}, fo);
+  Tensor patches = at::empty({n * m, 3, P, P}, fo), counts = at::empty({mode == DEVO_SELECT_NMS ? n : 0}, fo.dtype(at::kInt));
+  check(devo_patch_select(scores.data_ptr<float>(), scores.stride(0), scores.stride(1), scores.stride(2), (int)n, (int)h, (int)w, (int)m, (int)mode, grid ? 1 : 0, (int)k,
+                          pad ? 1 : 0, mode == DEVO_SELECT_MULTI ? noise->data_ptr<float>() : nullptr, mode == DEVO_SELECT_3XRANDOM ? i64p(*cand_x) : nullptr,
+                          mode == DEVO_SELECT_3XRANDOM ? i64p(*cand_y) : nullptr, (int)offset, clamp ? 1 : 0, (int)cx0, (int)cx1, (int)cy0, (int)cy1,
+                          has_disps ? disps->data_ptr<float>() : nullptr, has_disps ? disps->stride(0) : 0, has_disps ? disps->stride(1) : 0, has_disps ? disps->stride(2) : 0,
+                          has_disps ? (int)disps->size(1) : 0, has_disps ? (int)disps->size(2) : 0, (int)P, x.data_ptr<int64_t>(), y.data_ptr<int64_t>(), xy.data_ptr<float>(),
+                          sc.data_ptr<float>(), patches.data_ptr<float>(), index.data_ptr<int64_t>(), mode == DEVO_SELECT_NMS ? counts.data_ptr<int>() : nullptr,
+                          stream_of(scores)), "select");
+  return {x, y, xy, sc, patches, index, counts};
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -935,6 +975,8 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("frame_graph_disps(Tensor depths) -> Tensor");
   m.def("frame_graph_distances(Tensor poses, Tensor disps, Tensor intrinsics, float scale) -> Tensor");
   m.def("frame_graph_lists(Tensor matrix, float max_flow) -> Tensor[]");
+  m.def("patch_select(Tensor scores, int m, int mode, bool grid, int k, bool pad, Tensor? noise, Tensor? cand_x, Tensor? cand_y, int offset, bool clamp, int cx0, int cx1, "
+        "int cy0, int cy1, Tensor? disps, int P) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -957,6 +999,7 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("frame_graph_disps", &fg_disps);
   m.impl("frame_graph_distances", &fg_distances);
   m.impl("frame_graph_lists", &fg_lists);
+  m.impl("patch_select", &patch_select);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1021,6 +1064,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   fg.def("distances", &fg_distances);
   fg.def("lists", &fg_lists);
   fg.def("workspace_bytes", [](int64_t N, int64_t h, int64_t w) { return (int64_t)devo_frame_graph_workspace_bytes((int)N, (int)h, (int)w); });
+  auto sel = m.def_submodule("select", "devo_amd.select: devo/selector.py:50-287 and the tail of enet.py:100-200 in one launch");
+  sel.def("patch_select", &patch_select);
+  sel.attr("MAX_CELLS") = (int64_t)DEVO_SELECT_MAX_CELLS;
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

@@ -37,6 +37,7 @@ _GRAPH = os.environ.get("DEVO_PATCHIFIER_GRAPH", "1") != "0"      # 0: the encod
 _GRAPH_MAX_FRAMES = 2                                              # (beyond a frame or two the call is paced by the GPU: nothing to gain)
 _LOWP_CL = os.environ.get("DEVO_PATCHIFIER_LOWP_CL", "0") == "1"   # (experiment: the copy's weights in channels-last format)
 _LOWP = os.environ.get("DEVO_PATCHIFIER_LOWP", "1") != "0"        # 0: an autocast call converts the parameters itself, every call
+_SELECT = os.environ.get("DEVO_PATCHIFIER_SELECT", "1") != "0"    # 0: the patch selection and its tail as the torch composition below, always
 
 
 def _norm(kind, x):
@@ -466,7 +467,28 @@ class Patchifier(nn.Module):
         b, n, _, h, w = fmap.shape
         P, M, dev = self.patch_size, patches_per_image, fmap.device
         scores = None
-        if coords is not None:
+        # without gradients on the GPU the selection and everything derived from the centres is ONE launch (devo_amd.select: the padding, both
+        # poolings, the ranking, the mode, the score gather, xy, patches and index; plus the noise draw in 'multi', the two candidate draws in
+        # '3xrandom' and the read-back of the survivor counts in 'nms'); the functions above stay as its oracle and as the path with gradients
+        sel = None
+        if _SELECT and coords is None and fmap.is_cuda and not torch.is_grad_enabled() and self.patch_selector in ("scorer", "gradient"):
+            from . import select as S
+            if self.patch_selector == "gradient":
+                g = self.event_gradient(images).float()
+                rng = ((1, w - 2), (1, h - 2))
+                if candidates is not None:
+                    sel = S.select(g, M, "3xrandom", candidates=candidates, clamp=rng, disps=disps, P=P, pad=False)
+                else:
+                    sel = S.select(g, M, "3xrandom" if self.training else scorer_eval_mode, scorer_eval_use_grid, clamp=rng, disps=disps, P=P)
+            else:
+                smap = smap_lp if smap_lp is not None else torch.sigmoid(self.scorer(images).float())
+                if self.training:
+                    sel = S.select(smap, M, "3xrandom", candidates=candidates, disps=disps, P=P, pad=False)
+                else:
+                    sel = S.select(smap, M, scorer_eval_mode, scorer_eval_use_grid, offset=1, disps=disps, P=P)
+                scores = sel.scores
+            x, y, xy = sel.x, sel.y, sel.xy
+        elif coords is not None:
             x, y = coords
         elif self.patch_selector == "gradient":
             g = self.event_gradient(images)
@@ -490,26 +512,30 @@ class Patchifier(nn.Module):
         if self.patch_selector == "scorer" and coords is not None:
             smap = torch.sigmoid(self.scorer(images).float())
             scores = smap[0][torch.arange(n, device=dev)[:, None], (y - 1).clamp(0, h - 3), (x - 1).clamp(0, w - 3)]
-        xy = torch.stack([x, y], dim=-1).float()                                  # [n, M, 2], feature-map pixels
+        if sel is None:
+            xy = torch.stack([x, y], dim=-1).float()                              # [n, M, 2], feature-map pixels
         # (the kernel takes the channels-last strides: no NCHW copy; without gradients the gathers read the maps in their own precision and only the
         #  gathered patches are widened — the same values as widening 9.8 M map elements first)
         lazy = not torch.is_grad_enabled() and fmap.dtype in (torch.float16, torch.float32) and imap.dtype == fmap.dtype
         src_i, src_f = (imap[0], fmap[0]) if lazy else (imap[0].float(), fmap[0].float())
         imap_p = altcorr.patchify(src_i, xy, 0).float().view(b, -1, self.dim_inet, 1, 1)
         gmap = altcorr.patchify(src_f, xy, P // 2).float().view(b, -1, self.dim_fnet, P, P)
-        # patches = patchify(coords_grid_with_index(disps), xy, P // 2) in closed form: pixel (x + j - r, y + i - r) and its depth
-        r = P // 2
-        off = torch.arange(-r, r + 1, device=dev, dtype=torch.float32)
-        px = (xy[..., 0, None, None] + off[None, None, None, :]).expand(n, M, P, P)
-        py = (xy[..., 1, None, None] + off[None, None, :, None]).expand(n, M, P, P)
-        if disps is None:
-            pd = torch.ones(n, M, P, P, device=dev)
+        if sel is not None:
+            patches, index = sel.patches.view(b, n * M, 3, P, P), sel.index
         else:
-            pd = altcorr.patchify(disps[0, :, None].float().contiguous(), xy, r).view(n, M, P, P)
-            inside = (px >= 0) & (px < w) & (py >= 0) & (py < h)                  # (the gather returns 0 outside the frame; so does the grid's)
-            px, py = px * inside, py * inside
-        patches = torch.stack([px, py, pd], dim=2).view(b, n * M, 3, P, P)
-        index = torch.arange(n, device=dev).view(n, 1).repeat(1, M).reshape(-1)
+            # patches = patchify(coords_grid_with_index(disps), xy, P // 2) in closed form: pixel (x + j - r, y + i - r) and its depth
+            r = P // 2
+            off = torch.arange(-r, r + 1, device=dev, dtype=torch.float32)
+            px = (xy[..., 0, None, None] + off[None, None, None, :]).expand(n, M, P, P)
+            py = (xy[..., 1, None, None] + off[None, None, :, None]).expand(n, M, P, P)
+            if disps is None:
+                pd = torch.ones(n, M, P, P, device=dev)
+            else:
+                pd = altcorr.patchify(disps[0, :, None].float().contiguous(), xy, r).view(n, M, P, P)
+                inside = (px >= 0) & (px < w) & (py >= 0) & (py < h)              # (the gather returns 0 outside the frame; so does the grid's)
+                px, py = px * inside, py * inside
+            patches = torch.stack([px, py, pd], dim=2).view(b, n * M, 3, P, P)
+            index = torch.arange(n, device=dev).view(n, 1).repeat(1, M).reshape(-1)
         if self.training and self.patch_selector == "scorer":
             return fmap, gmap, imap_p, patches, index, scores
         if not self.training and return_color:

@@ -38,7 +38,7 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   so did devo_frame_begin, devo_frame_point_cloud, devo_frame_record_removed, devo_frame_record_skipped,
                                   devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
                                   devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes; and devo_frame_graph_disps,
-                                  devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes);
+                                  devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -848,6 +848,41 @@ int devo_frame_graph_distances (const float* poses, const float* disps, const fl
                                size_t ws_bytes, devo_stream_t stream);
 int devo_frame_graph_lists (const float* matrix, int N, float max_flow, int64_t* rowptr, int64_t* cols, float* dists, int64_t capacity, void* ws, size_t ws_bytes,
                            devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Patch selection (devo/selector.py:50-287, PatchSelector.__call__, and what devo/enet.py:100-200 derives from the chosen centres;
+ * csrc/select.hip; devo_amd/select.py): ONE launch, one workgroup per frame, no workspace.
+ *   scores   f32 [n, h, w] with ELEMENT strides (s_n, s_h, s_w).  The map is zero-padded (never materialised) to whole cells of k x k —
+ *            whole 2 x 2 grids of cells with `grid` — centred, the extra pixel of an odd padding at the bottom / right; pad = 0 (3xrandom
+ *            only) runs on the map as it is.  k must be 4; at most DEVO_SELECT_MAX_CELLS cells per frame, m <= DEVO_SELECT_MAX_CELLS
+ *            (3xrandom: 3 m): anything larger is DEVO_ERR_UNSUPPORTED.
+ *   ranking  everywhere: the higher key first, on equal keys the lower flat cell index first.  Bit-reproducible, no atomics.
+ *   TOPK     key = the cell's maximum; the m best cells (grid: m / 4 per quadrant, output k-major and quadrant-minor), pixel = the
+ *            first maximum of the cell in row-major order.
+ *   MULTI    noise f32 [n, C + 16 m] of Exp(1) draws, C = cells per frame (values <= 0 count as FLT_MIN).  Cell key
+ *            (mean + 1e-7f) / noise[cell] with grid, mean / noise[cell] without; the largest keys in decreasing order.  The pixel of
+ *            output slot s: offset o = first argmax_j (win[j] + 1e-7f) / noise[C + 16 s + j] over the 16 pixels that start one pixel
+ *            up-left of the cell (0 outside the padded map), applied to the cell's origin (the reference's arithmetic).
+ *   NMS      a 3 x 3 box at every cell's maximum (x1 = max(cx - 1.5, 0), x2 = x1 + 3), category = the frame, with grid the reference's
+ *            quadrant test (box corner in pixels < half the pooled size), greedy suppression at IoU > 0.4 in rank order; the first m
+ *            survivors, counts i32 [n] = survivors per frame; slots beyond the count repeat the frame's last survivor.  The suppression
+ *            is iterated over the whole map until nothing changes: (longest suppression chain + 1) rounds of one barrier each, at most
+ *            C + 1 (a monotonically decreasing chain of overlapping boxes through every cell): bounded, never a hang.
+ *   3XRANDOM cand_x, cand_y i64 [n, 3 m] on the (padded) map; their scores (0 in the padding) sorted ascending and stable, the last m;
+ *            out_scores = those scores, ascending; the winners leave as x + 1, y + 1 (the reference's _3xrandom).
+ *   epilogue x = clamp(x - left, 0, w - 1) (y alike; without the clamp when pad = 0), out_scores = the map there (all modes but
+ *            3XRANDOM), then x += offset, y += offset and, with `clamp`, x into [cx0, cx1], y into [cy0, cy1].
+ *   outputs  x, y i64 [n, m]; xy f32 [n, m, 2]; out_scores f32 [n, m]; index i64 [n m] (the frame); patches f32 [n m, 3, P, P]:
+ *            (x + j - P/2, y + i - P/2, 1) — with disps (f32 [n, H, W], element strides d_n, d_h, d_w) the depth there, and 0 in all
+ *            three planes outside H x W.  disps must have the size of the FRAME the centres live in (the feature map, which the entry
+ *            point does not see otherwise): H x W is both the gather's bound and the bound the coordinates are zeroed against.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_SELECT_MAX_CELLS 4096
+enum { DEVO_SELECT_TOPK = 0, DEVO_SELECT_MULTI = 1, DEVO_SELECT_NMS = 2, DEVO_SELECT_3XRANDOM = 3 };
+int devo_patch_select(const float* scores, int64_t s_n, int64_t s_h, int64_t s_w, int n, int h, int w, int m, int mode, int grid, int k, int pad,
+                      const float* noise, const int64_t* cand_x, const int64_t* cand_y, int offset, int clamp, int cx0, int cx1, int cy0, int cy1,
+                      const float* disps, int64_t d_n, int64_t d_h, int64_t d_w, int H, int W, int P, int64_t* x, int64_t* y, float* xy,
+                      float* out_scores, float* patches, int64_t* index, int* counts, devo_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -1,14 +1,21 @@
+"""The Patchifier's per-frame call (one 480 x 640 frame under autocast fp16, M = 96): host and wall time per call, launches and GPU time per
+call, and the call replayed from a captured graph.
+
+    python tools/probe_patchifier_frame.py [topk | multi | nms]        # the evaluation selection mode on the 2 x 2 grid (default topk)
+    DEVO_PATCHIFIER_SELECT=0 python tools/probe_patchifier_frame.py multi   # the same with the selection as the torch composition
+"""
 import os, sys, time
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 from devo_amd.patchifier import Patchifier
+MODE = sys.argv[1] if len(sys.argv) > 1 else "topk"
 dev = torch.device("cuda", 0)
 torch.manual_seed(0)
 pf = Patchifier().to(dev).eval()
 images = torch.randn(1, 1, 5, 480, 640, device=dev)
 def run():
     with torch.no_grad(), torch.autocast("cuda", dtype=torch.float16):
-        return pf(images, 96, scorer_eval_mode="topk")
+        return pf(images, 96, scorer_eval_mode=MODE)
 for _ in range(5): run()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
@@ -16,7 +23,7 @@ for _ in range(20): run()
 th = time.perf_counter() - t0
 torch.cuda.synchronize()
 ta = time.perf_counter() - t0
-print(f"eager: host {th/20*1e3:.3f} ms, wall {ta/20*1e3:.3f} ms")
+print(f"eager ({MODE}): host {th/20*1e3:.3f} ms, wall {ta/20*1e3:.3f} ms")
 from torch.profiler import profile, ProfilerActivity
 with profile(activities=[ProfilerActivity.CUDA]) as prof:
     for _ in range(5): run()
