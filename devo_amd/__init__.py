@@ -8,6 +8,8 @@ that walks it).
 
 `select` is the per-frame patch selection (the reference's PatchSelector and the Patchifier's tail behind it) as one launch.
 
+`evaluation` scores a finished trajectory: association with the ground truth, Sim(3) alignment and the ATE of a batch of pairs in one launch.
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """

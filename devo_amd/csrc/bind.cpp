@@ -818,6 +818,40 @@ TensorList patch_select(const Tensor& scores, int64_t m, int64_t mode, bool grid
   return {x, y, xy, sc, patches, index, counts};
 }
 
+// ------------------------------------------------------------------------------------------------ trajectory evaluation (devo_amd/evaluation.py; csrc/traj_eval.hip)
+// devo_traj_eval on tensors: packed poses [total, 7] (fp32 or fp64, both alike), stamps [total] (int64 or fp64, both alike), offsets i64 [B + 1] on
+// the GPU.  The outputs and the workspace are allocated here; the Python module packs, checks the offsets and reads the status.
+// -> {stats f64 [B, DEVO_TRAJ_EVAL_COLS], transform f64 [B, 8], status i32 [B], errors f64 [total_est] or [0], matched i32 [total_est] or [0]}
+TensorList traj_eval(const Tensor& est, const Tensor& est_stamps, const Tensor& est_off, const Tensor& gt, const Tensor& gt_stamps, const Tensor& gt_off, int64_t assoc,
+                     int64_t align, double max_diff, int64_t rpe_delta, bool want_errors, bool want_matched) {
+  require_gpu(est, est_stamps, est_off, gt, gt_stamps, gt_off);
+  for (const Tensor* t : {&est, &gt})
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == 7 && t->is_contiguous() && (t->scalar_type() == at::kFloat || t->scalar_type() == at::kDouble) &&
+                t->scalar_type() == est.scalar_type() && t->device() == est.device(), "evaluation: poses must be contiguous [N, 7] tensors of one dtype (float32 or float64) on one GPU");
+  for (const Tensor* t : {&est_stamps, &gt_stamps})
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous() && (t->scalar_type() == at::kLong || t->scalar_type() == at::kDouble) && t->scalar_type() == est_stamps.scalar_type() &&
+                t->device() == est.device(), "evaluation: stamps must be contiguous [N] tensors of one dtype (int64 or float64) on the poses' GPU");
+  TORCH_CHECK(est_stamps.numel() == est.size(0) && gt_stamps.numel() == gt.size(0), "evaluation: one stamp per pose expected");
+  pg_check_idx("evaluation", est_off);
+  pg_check_idx("evaluation", gt_off);
+  const int64_t B = est_off.numel() - 1;
+  TORCH_CHECK(B >= 1 && gt_off.numel() == B + 1 && B <= INT32_MAX && est_off.device() == est.device() && gt_off.device() == est.device(),
+              "evaluation: offsets must be two int64 [B + 1] tensors on the poses' GPU");
+  TORCH_CHECK(rpe_delta >= 0 && rpe_delta <= INT32_MAX, "evaluation: rpe_delta ", rpe_delta);
+  c10::DeviceGuard guard(est.device());
+  const auto fo = est.options().dtype(at::kDouble).memory_format(c10::nullopt);
+  const int64_t total_est = est.size(0);
+  Tensor stats = at::empty({B, DEVO_TRAJ_EVAL_COLS}, fo), transform = at::empty({B, 8}, fo), status = at::empty({B}, fo.dtype(at::kInt));
+  Tensor errors = at::empty({want_errors ? total_est : 0}, fo), matched = at::empty({want_matched ? total_est : 0}, fo.dtype(at::kInt));
+  const size_t bytes = devo_traj_eval_workspace_bytes(total_est, (int)assoc);
+  Tensor ws = at::empty({(int64_t)bytes}, fo.dtype(at::kByte));
+  check(devo_traj_eval(est.data_ptr(), est_stamps.data_ptr(), i64p(est_off), total_est, gt.data_ptr(), gt_stamps.data_ptr(), i64p(gt_off), gt.size(0), (int)B,
+                       dtype_code(est), est_stamps.scalar_type() == at::kDouble ? 1 : 0, (int)assoc, (int)align, max_diff, (int)rpe_delta, stats.data_ptr<double>(),
+                       transform.data_ptr<double>(), status.data_ptr<int>(), want_errors ? errors.data_ptr<double>() : nullptr,
+                       want_matched ? matched.data_ptr<int>() : nullptr, ws.data_ptr(), bytes, stream_of(est)), "evaluation");
+  return {stats, transform, status, errors, matched};
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -977,6 +1011,8 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("frame_graph_lists(Tensor matrix, float max_flow) -> Tensor[]");
   m.def("patch_select(Tensor scores, int m, int mode, bool grid, int k, bool pad, Tensor? noise, Tensor? cand_x, Tensor? cand_y, int offset, bool clamp, int cx0, int cx1, "
         "int cy0, int cy1, Tensor? disps, int P) -> Tensor[]");
+  m.def("traj_eval(Tensor est, Tensor est_stamps, Tensor est_off, Tensor gt, Tensor gt_stamps, Tensor gt_off, int assoc, int align, float max_diff, int rpe_delta, "
+        "bool want_errors, bool want_matched) -> Tensor[]");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -1000,6 +1036,7 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("frame_graph_distances", &fg_distances);
   m.impl("frame_graph_lists", &fg_lists);
   m.impl("patch_select", &patch_select);
+  m.impl("traj_eval", &traj_eval);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1067,6 +1104,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   auto sel = m.def_submodule("select", "devo_amd.select: devo/selector.py:50-287 and the tail of enet.py:100-200 in one launch");
   sel.def("patch_select", &patch_select);
   sel.attr("MAX_CELLS") = (int64_t)DEVO_SELECT_MAX_CELLS;
+  auto ev = m.def_submodule("evaluation", "devo_amd.evaluation: utils/eval_utils.py's ate / ate_real (association, Umeyama alignment, ATE) in one launch");
+  ev.def("traj_eval", &traj_eval);
+  ev.def("workspace_bytes", [](int64_t total_est, int64_t assoc) { return (int64_t)devo_traj_eval_workspace_bytes(total_est, (int)assoc); });
+  ev.attr("COLS") = (int64_t)DEVO_TRAJ_EVAL_COLS;
+  ev.attr("MAX_MATCHES") = (int64_t)DEVO_TRAJ_EVAL_MAX_MATCHES;
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

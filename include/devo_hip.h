@@ -38,7 +38,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   so did devo_frame_begin, devo_frame_point_cloud, devo_frame_record_removed, devo_frame_record_skipped,
                                   devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
                                   devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes; and devo_frame_graph_disps,
-                                  devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select);
+                                  devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select; and devo_traj_eval,
+                                  devo_traj_eval_workspace_bytes);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -883,6 +884,51 @@ int devo_patch_select(const float* scores, int64_t s_n, int64_t s_h, int64_t s_w
                       const float* noise, const int64_t* cand_x, const int64_t* cand_y, int offset, int clamp, int cx0, int cx1, int cy0, int cy1,
                       const float* disps, int64_t d_n, int64_t d_h, int64_t d_w, int H, int W, int P, int64_t* x, int64_t* y, float* xy,
                       float* out_scores, float* patches, int64_t* index, int* counts, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Trajectory evaluation (what utils/eval_utils.py's ate / ate_real / log_results obtain from evo: association, Umeyama alignment,
+ * ATE; csrc/traj_eval.hip; devo_amd/evaluation.py): ONE launch, one workgroup per pair of trajectories, all arithmetic fp64,
+ * fixed-order reductions (bit-reproducible, independent of B), no host synchronisation.
+ *   est, gt      poses [total_est, 7] / [total_gt, 7] as (t, q_xyzw), camera-to-world, contiguous, pose_dtype DEVO_F32 or DEVO_F64;
+ *                quaternions are normalised on load.  Pair b owns rows est_off[b] .. est_off[b + 1] and gt_off[b] .. gt_off[b + 1]
+ *                (int64 [B + 1] in DEVICE memory, checked against the totals by the kernel).
+ *   stamps       [total_est] / [total_gt], int64 (stamps_f64 = 0) or fp64 (1), compared after conversion to fp64; a magnitude
+ *                >= 2^53 or a non-finite stamp flags the pair (the conversion would not be exact).
+ *   assoc        NEAREST: the shorter trajectory (the ground truth at equal length) is the short one; short pose i takes the long index
+ *                j of the nearest stamp (the lowest j on equal distance, the leftmost of equal stamps) and is kept when the distance is
+ *                <= max_diff; matches stay in short order.  INTERPOLATE: every estimated stamp inside [gt[0], gt[-1]] gets the ground
+ *                truth interpolated between its bracketing poses (linear translation, shorter-arc slerp; a stamp that hits a ground-truth
+ *                stamp takes that pose, the leftmost of equal ones); the estimate is the short one, matched = the lower bracket.
+ *                The long stamps must be non-decreasing.
+ *   align        NONE, SE3, SIM3 of the estimate onto the ground truth (Umeyama 1991) over the n matched positions: means, sigma_x^2 =
+ *                mean |x - mean x|^2, Sigma = mean (y - mean y)(x - mean x)^T = U D V^T by a one-sided Jacobi iteration, S = diag(1, 1,
+ *                sign(det U det V)), R = U S V^T, c = tr(D S) / sigma_x^2 (1 for SE3), t = mean y - c R mean x.  The third singular
+ *                vectors are the cross products of the first two (a planar trajectory is valid).  n < 3 or sigma_2 <= 1e-10 sigma_1
+ *                is degenerate.  NONE needs n >= 1.
+ *   stats        fp64 [B, DEVO_TRAJ_EVAL_COLS], e_i = |y_i - (c R x_i + t)|:
+ *                0 n; 1 rmse; 2 mean; 3 median (the mean of the two middle values for even n; NaN if an error is NaN); 4 std (population,
+ *                two passes); 5 min; 6 max; 7 sse; 8 rot_rmse_deg, 9 rot_mean_deg (the angle of R_gt^T R R_est, 2 atan2(|q_v|, |q_w|));
+ *                10 path_length (the whole ground-truth trajectory of the pair, before association); 11 MPE = 100 mean / path_length;
+ *                12 scale c; 13 rpe_trans_rmse, 14 rpe_rot_rmse_deg over the matches k, k + rpe_delta (the estimate's translations scaled
+ *                by c, error pose (Q_k^-1 Q_k+d)^-1 (P_k^-1 P_k+d); NaN for rpe_delta = 0 or >= n); 15 the number of RPE terms.
+ *   transform    fp64 [B, 8] = (c, t, q_xyzw of R, w >= 0).
+ *   status       i32 [B]: 0 or DEVO_TRAJ_* flags.  A flagged pair has columns 1 .. 15 and its transform NaN; column 0 stays the
+ *                number of matches (0 when the association did not run).
+ *   errors_out   fp64 [total_est] or NULL: e per SHORT pose at est_off[b] + i (the short trajectory is never longer than the estimate),
+ *                NaN where unmatched and behind the short length.  matched_out i32 [total_est] or NULL: the long index, -1 likewise.
+ *   ws           devo_traj_eval_workspace_bytes(total_est, assoc) bytes, 16-byte aligned.
+ * At most DEVO_TRAJ_EVAL_MAX_MATCHES short poses per pair (more: the pair is flagged).
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_TRAJ_EVAL_COLS 16
+#define DEVO_TRAJ_EVAL_MAX_MATCHES 131072
+enum { DEVO_TRAJ_ALIGN_NONE = 0, DEVO_TRAJ_ALIGN_SE3 = 1, DEVO_TRAJ_ALIGN_SIM3 = 2 };
+enum { DEVO_TRAJ_ASSOC_NEAREST = 0, DEVO_TRAJ_ASSOC_INTERPOLATE = 1 };
+enum { DEVO_TRAJ_NO_MATCH = 1, DEVO_TRAJ_TOO_FEW = 2, DEVO_TRAJ_DEGENERATE = 4, DEVO_TRAJ_UNSORTED = 8, DEVO_TRAJ_TOO_LONG = 16, DEVO_TRAJ_STAMP_RANGE = 32,
+       DEVO_TRAJ_BAD_OFFSETS = 64 };
+size_t devo_traj_eval_workspace_bytes(int64_t total_est, int assoc);
+int devo_traj_eval(const void* est, const void* est_stamps, const int64_t* est_off, int64_t total_est, const void* gt, const void* gt_stamps,
+                   const int64_t* gt_off, int64_t total_gt, int B, int pose_dtype, int stamps_f64, int assoc, int align, double max_diff, int rpe_delta,
+                   double* stats, double* transform, int* status, double* errors_out, int* matched_out, void* ws, size_t ws_bytes, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
