@@ -10,7 +10,17 @@ that walks it).
 
 `evaluation` scores a finished trajectory: association with the ground truth, Sim(3) alignment and the ATE of a batch of pairs in one launch.
 
+`camera` turns a lens calibration into the tensors the rest takes: the rectification map of `events.voxel_grids`, undistorted points and
+undistorted frames (pinhole, radtan and equidistant models; what the reference obtains from OpenCV).
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    if name == "camera":                                   # devo_amd.camera without an import of its own; loaded on first use
+        import importlib
+        return importlib.import_module(".camera", __name__)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.abspath(os.environ["DEVO_LIB"]) if os.environ.get("DEVO_LIB") else os.path.join(_HERE, "lib", "libdevo_hip.so")
 
 DEVO_F32, DEVO_F16, DEVO_F64 = 0, 1, 2
+DEVO_U8 = 3                    # image dtype code of devo_image_remap
 ABI_VERSION = 9                # include/devo_hip.h DEVO_ABI_VERSION: a library of another version is refused (argument lists differ)
 CBLOCK_SPLIT8 = -8             # DEVO_CBLOCK_SPLIT8: fp32 level in the split-blocked format of devo_corr_pyramid_split
 PLAN_TAIL = 4104               # DEVO_CORR_PLAN_TAIL: a plan buffer that can hold a group plan has 2 n + 2 + PLAN_TAIL ints
@@ -20,6 +21,7 @@ PLAN_EDGES, PLAN_GROUPS = 0, 1
 _DT = {torch.float32: DEVO_F32, torch.float16: DEVO_F16, torch.float64: DEVO_F64}
 
 _c_i64p = ctypes.POINTER(ctypes.c_int64)
+_dp = ctypes.POINTER(ctypes.c_double)            # host arrays of calibration scalars (devo_camera_*)
 _vp, _i, _i64, _sz, _f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_size_t, ctypes.c_float
 
 # name -> argtypes (restype is int unless listed in _RESTYPE); mirrors include/devo_hip.h exactly
@@ -169,6 +171,11 @@ _SIGNATURES.update({
 _SIGNATURES.update({
     "devo_traj_eval_workspace_bytes": [_i64, _i],
     "devo_traj_eval": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+})
+_SIGNATURES.update({
+    "devo_camera_undistort_points": [_vp, _i64, _i, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _vp, _i, _vp, _vp],
+    "devo_camera_distort_points": [_vp, _i64, _i, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _vp, _i, _vp, _vp],
+    "devo_image_remap": [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp],
 })
 for _n in ("exp", "log", "inv"):
     _SIGNATURES[f"devo_se3_{_n}"] = [_vp, _vp, _i64, _i, _vp]

@@ -852,6 +852,60 @@ TensorList traj_eval(const Tensor& est, const Tensor& est_stamps, const Tensor& 
   return {stats, transform, status, errors, matched};
 }
 
+// ------------------------------------------------------------------------------------------------ camera models (devo_amd/camera.py; csrc/camera.hip)
+// devo_camera_undistort_points / devo_camera_distort_points on tensors: points [n, 2] (fp32 or fp64) or none (the H x W pixel grid, on GPU
+// `device`); K (4), dist, R (9 or empty), K_new (4 or empty) are host numbers.  -> {out [n, 2] or [H, W, 2], invalid i32 [1] or [0]}
+TensorList camera_points(const c10::optional<Tensor>& points, int64_t H, int64_t W, int64_t device, int64_t model, std::vector<double> K, std::vector<double> dist,
+                         std::vector<double> R, std::vector<double> K_new, bool distort, bool out_f64, bool count) {
+  const bool grid = !(points.has_value() && points->defined());
+  TORCH_CHECK(K.size() == 4 && (R.empty() || R.size() == 9) && (K_new.empty() || K_new.size() == 4), "camera: K and K_new have 4 entries, R has 9");
+  TORCH_CHECK(H >= 0 && W >= 0 && H <= INT32_MAX && W <= INT32_MAX && dist.size() <= 5, "camera: sizes");
+  int64_t n;
+  at::TensorOptions o;
+  if (grid) {
+    n = H * W;
+    o = at::TensorOptions().device(c10::Device(c10::kCUDA, (c10::DeviceIndex)device));
+  } else {
+    require_gpu(*points);
+    TORCH_CHECK(points->dim() == 2 && points->size(1) == 2 && points->is_contiguous() && (points->scalar_type() == at::kFloat || points->scalar_type() == at::kDouble),
+                "camera: points must be a contiguous [n, 2] tensor of float32 or float64");
+    n = points->size(0);
+    o = points->options().memory_format(c10::nullopt);
+  }
+  c10::DeviceGuard guard(o.device());
+  Tensor out = grid ? at::empty({H, W, 2}, o.dtype(out_f64 ? at::kDouble : at::kFloat)) : at::empty({n, 2}, o.dtype(out_f64 ? at::kDouble : at::kFloat));
+  Tensor invalid = count ? at::zeros({1}, o.dtype(at::kInt)) : at::empty({0}, o.dtype(at::kInt));
+  auto* fn = distort ? &devo_camera_distort_points : &devo_camera_undistort_points;
+  check(fn(grid ? nullptr : points->data_ptr(), n, (int)H, (int)W, grid ? DEVO_F64 : dtype_code(*points), (int)model, K.data(), dist.empty() ? nullptr : dist.data(),
+           (int)dist.size(), R.empty() ? nullptr : R.data(), K_new.empty() ? nullptr : K_new.data(), out.data_ptr(), out_f64 ? DEVO_F64 : DEVO_F32,
+           count ? invalid.data_ptr<int>() : nullptr, stream_of(out)), distort ? "camera.distort_points" : "camera.undistort_points");
+  return {out, invalid};
+}
+
+// devo_image_remap on tensors: images [B, H, W, C] (uint8 or float32, contiguous), map float32 [Ho, Wo, 2]; `out` [B, Ho, Wo, C] is allocated when absent
+Tensor image_remap(const Tensor& images, const Tensor& map, const c10::optional<Tensor>& out_, bool out_u8) {
+  require_gpu(images, map);
+  TORCH_CHECK(images.dim() == 4 && images.is_contiguous() && (images.scalar_type() == at::kByte || images.scalar_type() == at::kFloat) && images.numel() > 0,
+              "camera.remap: images must be a contiguous [B, H, W, C] tensor of uint8 or float32");
+  TORCH_CHECK(map.dim() == 3 && map.size(2) == 2 && map.is_contiguous() && map.scalar_type() == at::kFloat && map.device() == images.device() && map.numel() > 0,
+              "camera.remap: map must be a contiguous float32 [Ho, Wo, 2] tensor on the images' GPU");
+  const int64_t B = images.size(0), H = images.size(1), W = images.size(2), C = images.size(3), Ho = map.size(0), Wo = map.size(1);
+  TORCH_CHECK(B <= INT32_MAX && H <= INT32_MAX && W <= INT32_MAX && Ho <= INT32_MAX && Wo <= INT32_MAX, "camera.remap: sizes");
+  c10::DeviceGuard guard(images.device());
+  const auto dt = out_u8 ? at::kByte : at::kFloat;
+  Tensor out;
+  if (out_.has_value() && out_->defined()) {
+    out = *out_;
+    TORCH_CHECK(out.is_cuda() && out.device() == images.device() && out.scalar_type() == dt && out.is_contiguous() && out.sizes() == at::IntArrayRef({B, Ho, Wo, C}),
+                "camera.remap: out must be a contiguous [B, Ho, Wo, C] tensor of the output dtype on the images' GPU");
+  } else {
+    out = at::empty({B, Ho, Wo, C}, images.options().dtype(dt).memory_format(c10::nullopt));
+  }
+  check(devo_image_remap(images.data_ptr(), (int)B, (int)H, (int)W, (int)C, images.scalar_type() == at::kByte ? (int)DEVO_U8 : (int)DEVO_F32, map.data_ptr<float>(), (int)Ho, (int)Wo,
+                         out.data_ptr(), out_u8 ? (int)DEVO_U8 : (int)DEVO_F32, stream_of(images)), "camera.remap");
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -1013,6 +1067,9 @@ TORCH_LIBRARY(devo_hip, m) {
         "int cy0, int cy1, Tensor? disps, int P) -> Tensor[]");
   m.def("traj_eval(Tensor est, Tensor est_stamps, Tensor est_off, Tensor gt, Tensor gt_stamps, Tensor gt_off, int assoc, int align, float max_diff, int rpe_delta, "
         "bool want_errors, bool want_matched) -> Tensor[]");
+  m.def("camera_points(Tensor? points, int H, int W, int device, int model, float[] K, float[] dist, float[] R, float[] K_new, bool distort, bool out_f64, bool count) "
+        "-> Tensor[]");
+  m.def("image_remap(Tensor images, Tensor map, Tensor? out, bool out_u8) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -1037,6 +1094,8 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("frame_graph_lists", &fg_lists);
   m.impl("patch_select", &patch_select);
   m.impl("traj_eval", &traj_eval);
+  m.impl("camera_points", &camera_points);
+  m.impl("image_remap", &image_remap);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1109,6 +1168,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ev.def("workspace_bytes", [](int64_t total_est, int64_t assoc) { return (int64_t)devo_traj_eval_workspace_bytes(total_est, (int)assoc); });
   ev.attr("COLS") = (int64_t)DEVO_TRAJ_EVAL_COLS;
   ev.attr("MAX_MATCHES") = (int64_t)DEVO_TRAJ_EVAL_MAX_MATCHES;
+  auto cam = m.def_submodule("camera", "devo_amd.camera: rectification maps, point (un)distortion and image remap (what the reference takes from OpenCV)");
+  cam.def("points", &camera_points);
+  cam.def("remap", &image_remap);
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

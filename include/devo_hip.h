@@ -39,7 +39,7 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
                                   devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes; and devo_frame_graph_disps,
                                   devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select; and devo_traj_eval,
-                                  devo_traj_eval_workspace_bytes);
+                                  devo_traj_eval_workspace_bytes; and devo_camera_undistort_points, devo_camera_distort_points, devo_image_remap);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -929,6 +929,42 @@ size_t devo_traj_eval_workspace_bytes(int64_t total_est, int assoc);
 int devo_traj_eval(const void* est, const void* est_stamps, const int64_t* est_off, int64_t total_est, const void* gt, const void* gt_stamps,
                    const int64_t* gt_off, int64_t total_gt, int B, int pose_dtype, int stamps_f64, int assoc, int align, double max_diff, int rpe_delta,
                    double* stats, double* transform, int* status, double* errors_out, int* matched_out, void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Camera models (what the reference obtains from OpenCV: utils/load_utils.py:675-702, :1041-1058, scripts/pp_*.py, devo/stream.py:26,74;
+ * csrc/camera.hip; devo_amd/camera.py).  K, dist, R, K_new are HOST pointers to small fp64 arrays; they travel as kernel arguments (no
+ * device copy, no workspace, one launch per call).
+ *   model, dist  PINHOLE (n_dist 0), RADTAN (OpenCV's k1 k2 p1 p2 [k3]: n_dist 4 or 5), EQUIDISTANT (Kannala-Brandt / OpenCV fisheye
+ *                k1..k4: n_dist 4).  Any other count is refused.
+ *   K, K_new     (fx, fy, cx, cy), finite, focal lengths non-zero.  R: 3 x 3 row-major or NULL (identity).
+ *   points       DEVICE [n, 2] of in_dtype (DEVO_F32 / DEVO_F64), or NULL: the pixel grid x = 0 .. W - 1, y = 0 .. H - 1 in row-major
+ *                order, generated in the kernel (n must be H * W).  With points, H and W are not read.
+ *   out          DEVICE [n, 2] of out_dtype (DEVO_F32 / DEVO_F64); all arithmetic is fp64.  An invalid point is (NaN, NaN).
+ *   invalid_count  DEVICE int32 or NULL: the number of invalid points is ADDED (the caller zeroes it); one atomic per wave that has any.
+ * devo_camera_undistort_points: raw pixel -> ideal pixel.  x_d = K^-1 p; x = model^-1(x_d); x <- R x (divided by its third component);
+ *   out = K_new x, or x itself (normalised coordinates) when K_new is NULL.
+ *   RADTAN: Newton on the two-dimensional forward model with its analytic Jacobian J, from x = x_d, at most 30 iterations, until
+ *   |dx| + |dy| < 1e-12.  Valid iff it converges and det J > 0 at every iterate: the principal branch, which never crosses the fold of a
+ *   strongly distorted model.
+ *   EQUIDISTANT: theta_d = |x_d|; theta (1 + k1 theta^2 + k2 theta^4 + k3 theta^6 + k4 theta^8) = theta_d is solved on [0, theta_lim] by
+ *   Newton safeguarded by bisection, x = x_d tan(theta) / theta_d.  theta_lim = the smallest positive root of the left side's derivative
+ *   in (0, pi / 2], or pi / 2 (found on the host in fp64).  Valid iff theta_d < theta_d,max = the left side at theta_lim; theta_d = 0 -> 0.
+ * devo_camera_distort_points: ideal pixel in K_new (required) -> raw pixel.  x = K_new^-1 p; v = R^T (x, 1); invalid when v.z <= 0
+ *   (behind the camera); x = v / v.z; the forward model (closed form); out = K x_d.  EQUIDISTANT: theta = atan |x| > theta_lim is invalid.
+ * devo_image_remap: out[b, yo, xo, :] = the bilinear sample of images[b] at map[yo, xo] = (x, y) source coordinates.
+ *   images       DEVICE [B, H, W, C] channels-last, contiguous, in_dtype DEVO_U8 or DEVO_F32, C in 1 .. 4.  map fp32 [Ho, Wo, 2].
+ *   out          DEVICE [B, Ho, Wo, C], out_dtype DEVO_U8 or DEVO_F32.  fp32 weights from the fp32 coordinates (x - floor x: exact); a tap
+ *                outside the image contributes 0 (OpenCV's BORDER_CONSTANT), a NaN coordinate gives 0.  DEVO_U8 output rounds to
+ *                nearest even and saturates.  One thread per output pixel serves all channels and all B images.
+ * ---------------------------------------------------------------------------------------------- */
+enum { DEVO_CAM_PINHOLE = 0, DEVO_CAM_RADTAN = 1, DEVO_CAM_EQUIDISTANT = 2 };
+enum { DEVO_U8 = 3 }; /* image dtype code of devo_image_remap, beside DEVO_F32 */
+int devo_camera_undistort_points(const void* points, int64_t n, int H, int W, int in_dtype, int model, const double* K, const double* dist, int n_dist,
+                                 const double* R, const double* K_new, void* out, int out_dtype, int* invalid_count, devo_stream_t stream);
+int devo_camera_distort_points(const void* points, int64_t n, int H, int W, int in_dtype, int model, const double* K, const double* dist, int n_dist,
+                               const double* R, const double* K_new, void* out, int out_dtype, int* invalid_count, devo_stream_t stream);
+int devo_image_remap(const void* images, int B, int H, int W, int C, int in_dtype, const float* map, int Ho, int Wo, void* out, int out_dtype,
+                     devo_stream_t stream);
 
 #ifdef __cplusplus
 }
