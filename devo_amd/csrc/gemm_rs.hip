@@ -52,6 +52,11 @@ __global__ __launch_bounds__(256) void k_rs_pack_f16(const __half* __restrict__ 
   }
 }
 
+// Bytes of a buffer of fp16 rows as a descriptor's size: the range check works per dword, and with an odd K the dword of the LAST row's
+// last element straddles the end — it would read as zero and the element drop out of the product (measured).  The other half of that
+// dword lies inside the row pitch (an even one, above an odd K) and is zeroed like everything from K on.
+__device__ __forceinline__ unsigned rs_whole_dwords(int64_t bytes) { return (unsigned)((bytes + 3) & ~(int64_t)3); }
+
 // y[M, N] = act(x[M, K] W^T + bias) [+ residual], N = 384 NB.  grid = ceil(M / (16 MT)).  NK = K steps of 32 (K <= 32 NK).
 template <int MT, int NK>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4 : 1, MT <= 3 ? 4 : 8))) void k_rs_linear_f16(const __half* __restrict__ x, int64_t ldx, const rs_u4* __restrict__ wimg,
@@ -63,7 +68,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
   constexpr unsigned OFF_NONE = 0x80000000u;
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS;
-  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(x), 0, (unsigned)(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(x), 0, rs_whole_dwords(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(wimg), 0, (unsigned)((int64_t)NB * RS_NW * NK * RS_NT * 1024), 0x00020000);
   // ---- the rows: memory -> registers -> LDS (piece p = 16 bytes: row p / PPR, halves 8 (p % PPR) .. + 7)
   rs_u4 ap[AP];
@@ -228,6 +233,39 @@ __device__ __forceinline__ float rs_row16_sum(float v) {               // over t
   return v;
 }
 
+// LayerNorm statistics of a workgroup's 16 MT rows while their elements are accumulators (this lane: 12 columns of row 16 mt + mi): sums over
+// the lane's 12, the four lanes of the row, then the eight waves through LDS (part: [row][wave][sum | squares] floats) -> stat[row] =
+// mean | rstd.  Two passes, like every other LayerNorm of the operator: q / D - mean^2 in one pass loses a row whose |mean| is 190 times
+// its spread 1e-2 of its rstd to the cancellation (measured: tests/test_gpu_update_chains.py, the `offset` set).  Ends behind a barrier.
+// (Every lane adding the eight partials of its own rows — two barriers less — was measured too: 3 % of the operator slower, not faster.)
+template <int MT>
+__device__ __forceinline__ void rs_row_stats(const rs_f4 (&acc)[MT][RS_NT], float* part, float* stat, float eps, int tid, int wv, int mi, int kg) {
+  constexpr int ROWS = 16 * MT, D = 384;
+#pragma unroll
+  for (int pass = 0; pass < 2; pass++) {
+#pragma unroll
+    for (int mt = 0; mt < MT; mt++) {
+      const float mean = pass ? stat[2 * (16 * mt + mi)] : 0.f;
+      float s = 0.f;
+#pragma unroll
+      for (int t = 0; t < RS_NT; t++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) { const float d = acc[mt][t][r] - mean; s += pass ? d * d : d; }
+      s += __shfl_xor(s, 16);
+      s += __shfl_xor(s, 32);
+      if (kg == 0) part[((16 * mt + mi) * 8 + wv) * 2 + pass] = s;
+    }
+    __syncthreads();
+    if (tid < ROWS) {
+      float s = 0.f;
+#pragma unroll
+      for (int w = 0; w < 8; w++) s += part[(tid * 8 + w) * 2 + pass];
+      stat[2 * tid + pass] = pass ? rsqrtf(s / (float)D + eps) : s / (float)D;
+    }
+    __syncthreads();
+  }
+}
+
 struct RsGru {
   const __half* x; const __half* hy; const int* grp;                   // rows: x[e] + hy[grp[e]]
   const __half* ln0_g; const __half* ln0_b;
@@ -252,7 +290,7 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
   unsigned char* X = rs_lds;
   unsigned char* R = rs_lds + ROWS * PITCH;
   _Float16* vec = reinterpret_cast<_Float16*>(rs_lds + 2 * ROWS * PITCH);
-  float* part = reinterpret_cast<float*>(rs_lds + 2 * ROWS * PITCH + RG_VEC * 2);      // [row][wave][sum | sum of squares]
+  float* part = reinterpret_cast<float*>(rs_lds + 2 * ROWS * PITCH + RG_VEC * 2);      // [row][wave][sum | sum of squared differences]
   float* stat = part + ROWS * 16;                                                        // [row][mean | rstd]
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS, E = a.E;
@@ -389,28 +427,8 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       }
     }
     if (rep == 0) {
-      // ---- X = LN2(t): a row's sums over this wave's 48 columns (12 in this lane, then over the four lanes of the row), then over the
-      //      eight waves through LDS
-#pragma unroll
-      for (int mt = 0; mt < MT; mt++) {
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int t = 0; t < RS_NT; t++)
-#pragma unroll
-          for (int r = 0; r < 4; r++) { s += acc[mt][t][r]; q += acc[mt][t][r] * acc[mt][t][r]; }
-        s += __shfl_xor(s, 16); q += __shfl_xor(q, 16);
-        s += __shfl_xor(s, 32); q += __shfl_xor(q, 32);
-        if (kg == 0) { part[((16 * mt + mi) * 8 + wv) * 2] = s; part[((16 * mt + mi) * 8 + wv) * 2 + 1] = q; }
-      }
-      __syncthreads();
-      if (tid < ROWS) {
-        float s = 0.f, q = 0.f;
-#pragma unroll
-        for (int w = 0; w < 8; w++) { s += part[(tid * 8 + w) * 2]; q += part[(tid * 8 + w) * 2 + 1]; }
-        const float mean = s / (float)D, var = fmaxf(q / (float)D - mean * mean, 0.f);
-        stat[2 * tid] = mean; stat[2 * tid + 1] = rsqrtf(var + a.eps2);
-      }
-      __syncthreads();
+      // ---- X = LN2(t)
+      rs_row_stats<MT>(acc, part, stat, a.eps2, tid, wv, mi, kg);
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) {
         const rs_f4 g = vec4(2304, t), bb = vec4(2688, t);
@@ -658,7 +676,7 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS, E = a.E, K0 = a.K0;
   const unsigned bvoff = (unsigned)lane * 16u;
-  const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.corr), 0, (unsigned)(((int64_t)(E - 1) * a.ldc + K0) * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.corr), 0, rs_whole_dwords(((int64_t)(E - 1) * a.ldc + K0) * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w0), 0, (unsigned)(D * NK0 * 32 * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w2), 0, (unsigned)(D * D * 2), 0x00020000);
   const __amdgpu_buffer_rsrc_t rs5 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w5), 0, (unsigned)(D * D * 2), 0x00020000);
@@ -746,26 +764,7 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) acc[mt][t] = rs_cvt4(rs_pack4(acc[mt][t] + bs));      // (rounded where the layer-by-layer path stores it)
   }
-#pragma unroll
-  for (int mt = 0; mt < MT; mt++) {
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int t = 0; t < RS_NT; t++)
-#pragma unroll
-      for (int r = 0; r < 4; r++) { s += acc[mt][t][r]; q += acc[mt][t][r] * acc[mt][t][r]; }
-    s += __shfl_xor(s, 16); q += __shfl_xor(q, 16);
-    s += __shfl_xor(s, 32); q += __shfl_xor(q, 32);
-    if (kg == 0) { part[((16 * mt + mi) * 8 + wv) * 2] = s; part[((16 * mt + mi) * 8 + wv) * 2 + 1] = q; }
-  }
-  __syncthreads();
-  if (tid < ROWS) {
-    float s = 0.f, q = 0.f;
-#pragma unroll
-    for (int w = 0; w < 8; w++) { s += part[(tid * 8 + w) * 2]; q += part[(tid * 8 + w) * 2 + 1]; }
-    const float mean = s / (float)D, var = fmaxf(q / (float)D - mean * mean, 0.f);
-    stat[2 * tid] = mean; stat[2 * tid + 1] = rsqrtf(var + a.eps3);
-  }
-  __syncthreads();
+  rs_row_stats<MT>(acc, part, stat, a.eps3, tid, wv, mi, kg);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
     const rs_f4 g = vec4(768, t), bb = vec4(1152, t);
@@ -1138,6 +1137,7 @@ int devo_upd_rs_linear_f16(const void* x, int64_t ldx, const void* wimg, const v
   DEVO_REQUIRE(devo_upd_rs_supported(N, K), "devo_upd_rs_linear_f16: N (%d) must be a multiple of 384 and K (%d) in (352, 384]", N, K);
   DEVO_REQUIRE(!(ldy & 7) && !(reinterpret_cast<uintptr_t>(y) & 15) && !(reinterpret_cast<uintptr_t>(residual) & 15) && !(ldx & 1) && !(reinterpret_cast<uintptr_t>(x) & 3),
                "devo_upd_rs_linear_f16: alignment (y / residual rows 16 bytes, x rows 4 bytes)");
+  DEVO_REQUIRE(ldx >= K, "devo_upd_rs_linear_f16: rows of %d elements at a pitch of %lld", K, (long long)ldx);
   DEVO_REQUIRE(((int64_t)(M - 1) * ldx + K) * 2 < (1ll << 31), "devo_upd_rs_linear_f16: x beyond 2 GB");
   const int NB = N / RS_BN;
   if (relu_from < 0) relu_from = 0;
@@ -1229,13 +1229,14 @@ int devo_upd_rs_expand_fg_f16(void* x, const void* hy, const int* group_of, cons
 }
 
 // The correlation branch and the first LayerNorm of the update operator as one launch, fp16 storage (enet.py:59-66, 82-83):
-//   c = l5(relu(LN3(l2(relu(l0(corr))))));  out = LN(net + inp + c).   corr [E, K0] with 768 < K0 <= 896 (DEVO: 882), rows 4-byte aligned; net / inp /
+//   c = l5(relu(LN3(l2(relu(l0(corr))))));  out = LN(net + inp + c).   corr [E, K0] with 864 < K0 <= 896 (28 K steps of 32; DEVO: 882), rows 4-byte aligned; net / inp /
 //   out [E, 384] contiguous; weight images of devo_upd_rs_pack_weight_f16 ([384, K0], [384, 384], [384, 384]); vectors fp16, 16-byte aligned.
 static int rs_corr_impl(const void* corr, int64_t ldc, int K0, const void* w0img, const void* b0, const void* w2img, const void* b2, const void* ln3_w,
                         const void* ln3_b, float eps3, const void* w5img, const void* b5, const void* net, const void* inp, const void* ln_w, const void* ln_b,
                         float eps, void* out, int E, void* stream, bool net32) {
   DEVO_REQUIRE(corr && w0img && b0 && w2img && b2 && ln3_w && ln3_b && w5img && b5 && net && inp && ln_w && ln_b && out && E > 0, "devo_upd_rs_corr_f16: null argument");
-  DEVO_REQUIRE(K0 > 768 && K0 <= 896 && ldc >= K0 && ldc % 2 == 0 && (reinterpret_cast<uintptr_t>(corr) & 3) == 0, "devo_upd_rs_corr_f16: 768 < K0 (%d) <= 896, rows 4-byte aligned", K0);
+  // (the kernel walks l0's image with 28 K steps per wave: the image of a narrower layer has fewer, and every wave but the first would read another's weights)
+  DEVO_REQUIRE(K0 > 864 && K0 <= 896 && ldc >= K0 && ldc % 2 == 0 && (reinterpret_cast<uintptr_t>(corr) & 3) == 0, "devo_upd_rs_corr_f16: 864 < K0 (%d) <= 896, rows 4-byte aligned", K0);
   DEVO_REQUIRE(((reinterpret_cast<uintptr_t>(net) | reinterpret_cast<uintptr_t>(inp) | reinterpret_cast<uintptr_t>(out) | reinterpret_cast<uintptr_t>(ln_w) |
                  reinterpret_cast<uintptr_t>(ln_b) | reinterpret_cast<uintptr_t>(w0img) | reinterpret_cast<uintptr_t>(w2img) | reinterpret_cast<uintptr_t>(w5img)) & 15) == 0,
                "devo_upd_rs_corr_f16: 16-byte alignment");

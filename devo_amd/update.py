@@ -695,9 +695,9 @@ def _rs_rows_ok(dt, dim):
 
 
 def _rs_chain_ok(dt, dim, x, inp2, c):
-    """this call can take the whole row-resident chain (Update._forward_rs): a correlation width of 769 - 896 in 4-byte aligned rows, the
+    """this call can take the whole row-resident chain (Update._forward_rs): a correlation width of 865 - 896 (the 28 K steps of the chain kernel) in 4-byte aligned rows, the
     state x and the context inp2 16-byte aligned"""
-    return (_rs_rows_ok(dt, dim) and 768 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0 and c.data_ptr() % 4 == 0
+    return (_rs_rows_ok(dt, dim) and 864 < c.shape[1] <= 896 and c.stride(1) == 1 and c.stride(0) % 2 == 0 and c.data_ptr() % 4 == 0
             and inp2.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0)
 
 

@@ -534,7 +534,7 @@ int devo_upd_rs_mlp2_fg_f16(const void* x, int64_t ldx, int x_rows, const int64_
  * SoftAgg that follows on the same rows, one launch: x [M, 384] contiguous, hy [groups, 384], fg [M, 768]. */
 int devo_upd_rs_expand_fg_f16(void* x, const void* hy, const int* group_of, const void* wfg_image, const void* bfg, void* fg, int M, void* stream);
 /* The correlation branch and the first LayerNorm of the update operator as ONE launch, fp16 storage (enet.py:59-66, 82-83):
- *   c = l5(relu(LN3(l2(relu(l0(corr))))));  out = LN(net + inp + c).   corr [E, K0], 768 < K0 <= 896 (DEVO: 882), rows 4-byte aligned; net / inp / out
+ *   c = l5(relu(LN3(l2(relu(l0(corr))))));  out = LN(net + inp + c).   corr [E, K0], 864 < K0 <= 896 (28 K steps of 32; DEVO: 882), rows 4-byte aligned; net / inp / out
  * [E, 384] contiguous; weight images of devo_upd_rs_pack_weight_f16 ([384, K0], [384, 384], [384, 384]); vectors fp16, 16-byte aligned. */
 int devo_upd_rs_corr_f16(const void* corr, int64_t ldc, int K0, const void* w0image, const void* b0, const void* w2image, const void* b2, const void* ln3_w,
                          const void* ln3_b, float eps3, const void* w5image, const void* b5, const void* net, const void* inp, const void* ln_w, const void* ln_b,
