@@ -13,6 +13,9 @@ that walks it).
 `camera` turns a lens calibration into the tensors the rest takes: the rectification map of `events.voxel_grids`, undistorted points and
 undistorted frames (pinhole, radtan and equidistant models; what the reference obtains from OpenCV).
 
+`simulate` makes the training data's events: contrast-threshold events from log-intensity frames (`ESIM`, the reference's esim_torch.ESIM),
+`log_intensity` in front of it and `frames_to_voxels` behind it (the loop of the reference's scripts/convert_tartan.py).
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """
@@ -20,7 +23,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name == "camera":                                   # devo_amd.camera without an import of its own; loaded on first use
+    if name in ("camera", "simulate"):                     # devo_amd.camera / devo_amd.simulate without an import of their own; loaded on first use
         import importlib
-        return importlib.import_module(".camera", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

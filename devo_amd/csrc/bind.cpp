@@ -906,6 +906,88 @@ Tensor image_remap(const Tensor& images, const Tensor& map, const c10::optional<
   return out;
 }
 
+// ------------------------------------------------------------------------------------------------ event simulation (devo_amd/simulate.py; csrc/esim.hip)
+// Thin forms of the devo_esim_* entry points: prev [H, W] and frames [T, H, W] fp32, prev_stamp [1] and stamps [T] int64, ref [H, W] fp64,
+// last_t [H, W] int64, all contiguous on one GPU.  The Python module owns the state, reads the status word, scans the counts and sorts the keys.
+void esim_inputs(const char* what, const Tensor& prev, const Tensor& frames, const Tensor& prev_stamp, const Tensor& stamps, const Tensor& ref, const Tensor& last_t) {
+  require_gpu(prev, frames, prev_stamp, stamps, ref, last_t);
+  TORCH_CHECK(frames.dim() == 3 && frames.size(0) >= 1 && frames.size(0) <= INT32_MAX && frames.size(1) <= INT32_MAX && frames.size(2) <= INT32_MAX &&
+              frames.scalar_type() == at::kFloat && frames.is_contiguous(), what, ": frames must be a contiguous float32 [T, H, W] tensor");
+  const int64_t T = frames.size(0), HW = frames.size(1) * frames.size(2);
+  TORCH_CHECK(prev.scalar_type() == at::kFloat && prev.numel() == HW && prev.is_contiguous() && ref.scalar_type() == at::kDouble && ref.numel() == HW && ref.is_contiguous() &&
+              last_t.scalar_type() == at::kLong && last_t.numel() == HW && last_t.is_contiguous(), what, ": prev float32, ref float64 and last_t int64 must be contiguous [H, W]");
+  TORCH_CHECK(prev_stamp.scalar_type() == at::kLong && prev_stamp.numel() == 1 && stamps.scalar_type() == at::kLong && stamps.numel() == T && stamps.is_contiguous(), what,
+              ": prev_stamp [1] and stamps [T] must be int64");
+  for (const Tensor* t : {&prev, &prev_stamp, &stamps, &ref, &last_t}) TORCH_CHECK(t->device() == frames.device(), what, ": tensors on different devices");
+}
+
+TensorList esim_count(const Tensor& prev, const Tensor& frames, const Tensor& prev_stamp, const Tensor& stamps, const Tensor& ref, const Tensor& last_t, double c_neg,
+                      double c_pos, int64_t refractory_ns) {
+  esim_inputs("simulate.count", prev, frames, prev_stamp, stamps, ref, last_t);
+  c10::DeviceGuard guard(frames.device());
+  const auto lo = frames.options().dtype(at::kLong).memory_format(c10::nullopt);
+  Tensor counts = at::empty({frames.size(1) * frames.size(2)}, lo), status_span = at::empty({2}, lo);
+  check(devo_esim_count(prev.data_ptr<float>(), frames.data_ptr<float>(), prev_stamp.data_ptr<int64_t>(), stamps.data_ptr<int64_t>(), (int)frames.size(0), (int)frames.size(1),
+                        (int)frames.size(2), ref.data_ptr<double>(), last_t.data_ptr<int64_t>(), c_neg, c_pos, refractory_ns, counts.data_ptr<int64_t>(),
+                        status_span.data_ptr<int64_t>(), stream_of(frames)), "simulate.count");
+  return {counts, status_span};
+}
+
+// -> {keys [total] (unsorted), ref_out, last_t_out}
+TensorList esim_emit(const Tensor& prev, const Tensor& frames, const Tensor& prev_stamp, const Tensor& stamps, const Tensor& ref, const Tensor& last_t, double c_neg,
+                     double c_pos, int64_t refractory_ns, const Tensor& offsets, int64_t total) {
+  esim_inputs("simulate.emit", prev, frames, prev_stamp, stamps, ref, last_t);
+  TORCH_CHECK(offsets.is_cuda() && offsets.device() == frames.device() && offsets.scalar_type() == at::kLong && offsets.numel() == ref.numel() && offsets.is_contiguous() && total >= 0,
+              "simulate.emit: offsets must be a contiguous int64 [H * W] tensor on the frames' GPU");
+  c10::DeviceGuard guard(frames.device());
+  Tensor keys = at::empty({total}, offsets.options().memory_format(c10::nullopt)), ref_out = at::empty_like(ref), last_out = at::empty_like(last_t);
+  check(devo_esim_emit(prev.data_ptr<float>(), frames.data_ptr<float>(), prev_stamp.data_ptr<int64_t>(), stamps.data_ptr<int64_t>(), (int)frames.size(0), (int)frames.size(1),
+                       (int)frames.size(2), ref.data_ptr<double>(), last_t.data_ptr<int64_t>(), c_neg, c_pos, refractory_ns, offsets.data_ptr<int64_t>(), total,
+                       total ? keys.data_ptr<int64_t>() : nullptr, ref_out.data_ptr<double>(), last_out.data_ptr<int64_t>(), stream_of(frames)), "simulate.emit");
+  return {keys, ref_out, last_out};
+}
+
+// the call's keys in ascending order: rocPRIM's keys-only radix sort over the bits a call of `span_ns` can set (devo_esim_sort_keys)
+Tensor esim_sort(const Tensor& keys, int64_t H, int64_t W, int64_t span_ns) {
+  require_gpu(keys);
+  TORCH_CHECK(keys.dim() == 1 && keys.scalar_type() == at::kLong && keys.is_contiguous() && H >= 1 && W >= 1 && H <= INT32_MAX && W <= INT32_MAX, "simulate.sort: keys int64 [N]");
+  c10::DeviceGuard guard(keys.device());
+  const int64_t n = keys.numel();
+  Tensor sorted = at::empty_like(keys);
+  if (n == 0) return sorted;
+  const size_t bytes = devo_esim_sort_workspace_bytes(n, (int)H, (int)W, span_ns);
+  Tensor ws = at::empty({(int64_t)bytes}, keys.options().dtype(at::kByte).memory_format(c10::nullopt));
+  check(devo_esim_sort_keys(keys.data_ptr<int64_t>(), sorted.data_ptr<int64_t>(), n, (int)H, (int)W, span_ns, bytes ? ws.data_ptr() : nullptr, bytes, stream_of(keys)),
+        "simulate.sort");
+  return sorted;
+}
+
+// sorted keys -> {x int16, y int16, t int64, p int8}
+TensorList esim_decode(const Tensor& keys, int64_t H, int64_t W, const Tensor& first_stamp) {
+  require_gpu(keys, first_stamp);
+  TORCH_CHECK(keys.dim() == 1 && keys.scalar_type() == at::kLong && keys.is_contiguous() && first_stamp.scalar_type() == at::kLong && first_stamp.numel() == 1 &&
+              first_stamp.device() == keys.device() && H >= 1 && W >= 1 && H <= INT32_MAX && W <= INT32_MAX, "simulate.decode: keys int64 [N], first_stamp int64 [1] on one GPU");
+  c10::DeviceGuard guard(keys.device());
+  const int64_t n = keys.numel();
+  const auto o = keys.options().memory_format(c10::nullopt);
+  Tensor x = at::empty({n}, o.dtype(at::kShort)), y = at::empty({n}, o.dtype(at::kShort)), t = at::empty({n}, o), p = at::empty({n}, o.dtype(at::kChar));
+  check(devo_esim_decode(n ? keys.data_ptr<int64_t>() : nullptr, n, (int)H, (int)W, first_stamp.data_ptr<int64_t>(), n ? x.data_ptr<int16_t>() : nullptr,
+                         n ? y.data_ptr<int16_t>() : nullptr, n ? t.data_ptr<int64_t>() : nullptr, n ? (signed char*)p.data_ptr<int8_t>() : nullptr, stream_of(keys)),
+        "simulate.decode");
+  return {x, y, t, p};
+}
+
+Tensor log_intensity(const Tensor& images, const Tensor& table) {
+  require_gpu(images, table);
+  TORCH_CHECK(images.scalar_type() == at::kByte && images.is_contiguous() && table.scalar_type() == at::kFloat && table.numel() == 256 && table.is_contiguous() &&
+              table.device() == images.device(), "simulate.log_intensity: images contiguous uint8, table float32 [256] on the images' GPU");
+  c10::DeviceGuard guard(images.device());
+  Tensor out = at::empty(images.sizes(), images.options().dtype(at::kFloat).memory_format(c10::nullopt));
+  const int64_t n = images.numel();
+  check(devo_log_intensity(n ? images.data_ptr<uint8_t>() : nullptr, n, table.data_ptr<float>(), out.data_ptr<float>(), stream_of(images)), "simulate.log_intensity");
+  return out;
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -1070,6 +1152,12 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("camera_points(Tensor? points, int H, int W, int device, int model, float[] K, float[] dist, float[] R, float[] K_new, bool distort, bool out_f64, bool count) "
         "-> Tensor[]");
   m.def("image_remap(Tensor images, Tensor map, Tensor? out, bool out_u8) -> Tensor");
+  m.def("esim_count(Tensor prev, Tensor frames, Tensor prev_stamp, Tensor stamps, Tensor ref, Tensor last_t, float c_neg, float c_pos, int refractory_ns) -> Tensor[]");
+  m.def("esim_emit(Tensor prev, Tensor frames, Tensor prev_stamp, Tensor stamps, Tensor ref, Tensor last_t, float c_neg, float c_pos, int refractory_ns, Tensor offsets, "
+        "int total) -> Tensor[]");
+  m.def("esim_sort(Tensor keys, int H, int W, int span_ns) -> Tensor");
+  m.def("esim_decode(Tensor keys, int H, int W, Tensor first_stamp) -> Tensor[]");
+  m.def("log_intensity(Tensor images, Tensor table) -> Tensor");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -1096,6 +1184,11 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("traj_eval", &traj_eval);
   m.impl("camera_points", &camera_points);
   m.impl("image_remap", &image_remap);
+  m.impl("esim_count", &esim_count);
+  m.impl("esim_emit", &esim_emit);
+  m.impl("esim_sort", &esim_sort);
+  m.impl("esim_decode", &esim_decode);
+  m.impl("log_intensity", &log_intensity);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1171,6 +1264,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   auto cam = m.def_submodule("camera", "devo_amd.camera: rectification maps, point (un)distortion and image remap (what the reference takes from OpenCV)");
   cam.def("points", &camera_points);
   cam.def("remap", &image_remap);
+  auto sim = m.def_submodule("simulate", "devo_amd.simulate: contrast-threshold event simulation (the reference's esim_torch.ESIM in scripts/convert_tartan.py)");
+  sim.def("count", &esim_count);
+  sim.def("emit", &esim_emit);
+  sim.def("sort", &esim_sort);
+  sim.def("decode", &esim_decode);
+  sim.def("log_intensity", &log_intensity);
+  sim.def("max_span_ns", [](int64_t H, int64_t W) { return (H > INT32_MAX || W > INT32_MAX) ? (int64_t)0 : devo_esim_max_span_ns((int)H, (int)W); });
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

@@ -39,7 +39,9 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   devo_frame_complete, devo_frame_complete_workspace_bytes, devo_frame_complete_launches; and devo_train_graph_init,
                                   devo_train_graph_grow, devo_train_graph_net_backward, devo_train_graph_workspace_bytes; and devo_frame_graph_disps,
                                   devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select; and devo_traj_eval,
-                                  devo_traj_eval_workspace_bytes; and devo_camera_undistort_points, devo_camera_distort_points, devo_image_remap);
+                                  devo_traj_eval_workspace_bytes; and devo_camera_undistort_points, devo_camera_distort_points, devo_image_remap;
+                                  and devo_esim_count, devo_esim_emit, devo_esim_sort_keys, devo_esim_sort_workspace_bytes, devo_esim_decode, devo_esim_max_span_ns,
+                                  devo_log_intensity);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -965,6 +967,55 @@ int devo_camera_distort_points(const void* points, int64_t n, int H, int W, int 
                                const double* R, const double* K_new, void* out, int out_dtype, int* invalid_count, devo_stream_t stream);
 int devo_image_remap(const void* images, int B, int H, int W, int C, int in_dtype, const float* map, int Ho, int Wo, void* out, int out_dtype,
                      devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Event simulation: contrast-threshold events from consecutive log-intensity frames (what the reference's scripts/convert_tartan.py:198-297
+ * obtains from esim_torch.ESIM; csrc/esim.hip; devo_amd/simulate.py).  All pointers are DEVICE pointers.
+ * State per pixel: ref (fp64 reference level) and last_t (int64 stamp of its last emitted event, DEVO_ESIM_NO_EVENT before the first).
+ * One frame pair with fp32 log-intensities i0, i1 (widened to fp64) and int64 nanosecond stamps t0 < t1, dt = t1 - t0:
+ *   d = i1 - ref;  d >= 0: pol = +1, C = c_pos, n = floor(d / C);  otherwise pol = -1, C = c_neg, n = floor(-d / C)
+ *   k = 1 .. n:  L_k = ref + pol * (k * C)   (the product rounded, then the sum);
+ *                f = (L_k - i0) / (i1 - i0) clamped to [0, 1], f = 1 when i1 == i0;   t_k = t0 + (int64) floor(f * (double) dt);
+ *                the event is emitted iff last_t is DEVO_ESIM_NO_EVENT or t_k - last_t >= refractory_ns, and then last_t = t_k
+ *   ref = L_n when n > 0 (a suppressed event still moves the reference).
+ * fp64 with one rounding per operation in this order, nothing contracted: the output is bit-comparable with a host restatement.
+ * A call covers T pairs: (prev, frames[0]), (frames[0], frames[1]), ...; prev_stamp [1] and stamps [T] are the frames' stamps.
+ *   devo_esim_count   walks every pixel over the T pairs WITHOUT writing events or state.  counts [H * W] int64: emitted events per pixel;
+ *                     status_span [2] int64 (zeroed by the call): [0] DEVO_ESIM_* status bits, [1] the call's span stamps[T - 1] - *prev_stamp.
+ *                     With a status bit set the rest means nothing and devo_esim_emit must not follow.
+ *   devo_esim_emit    the same walk from the same state.  offsets [H * W] = the INCLUSIVE scan of counts, total = its last entry; event e of
+ *                     pixel i goes to keys[offsets[i - 1] + e] (never outside [offsets[i - 1], min(offsets[i], total))) as
+ *                     key = (t - *prev_stamp) << (b + 1) | i << 1 | (pol > 0),  b = the bits of H * W - 1 (at least 1), i = y * W + x:
+ *                     the keys' integer order is the events' total order (t, i, pol) with -1 before +1.  The new state goes to ref_out /
+ *                     last_t_out, which must not alias the old one.
+ *   devo_esim_sort_keys  keys [n] -> sorted [n] (not in place): rocPRIM's keys-only radix sort over bits 0 .. b + 1 + the bits of span_ns,
+ *                     where span_ns >= the largest stamp of a key (the count pass reports the call's span); ws of at least
+ *                     devo_esim_sort_workspace_bytes(n, H, W, span_ns) bytes (0: refused arguments, or no device to ask), else
+ *                     DEVO_ERR_WORKSPACE.
+ *   devo_esim_decode  sorted keys -> x, y int16, t int64 (= *first_stamp + the key's stamp), p int8 in {-1, +1}.
+ *   devo_esim_max_span_ns  the limit of the key: stamps[T - 1] - *prev_stamp must be below 2^(62 - b) ns (0 for a refused frame size).
+ * Limits, refused with DEVO_ERR_ARG before any launch: 1 <= H, W <= DEVO_ESIM_MAX_SIDE (int16 coordinates); thresholds finite and
+ * >= DEVO_ESIM_MIN_THRESHOLD; refractory_ns >= 0.  Found on the device and reported in the status word: a non-finite intensity
+ * (NONFINITE), stamps not strictly increasing (STAMPS), a span at or above the key's limit (SPAN), more than DEVO_ESIM_MAX_CROSSINGS levels
+ * crossed by one pixel in one pair (CROSSINGS; log_intensity frames with the smallest threshold cross 11 513).
+ * devo_log_intensity: out[i] = table[images[i]], table fp32 [256] (the host's np.log(v / 255 + 1e-5) in fp32: convert_tartan.py:244).
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_ESIM_NO_EVENT INT64_MIN
+#define DEVO_ESIM_MAX_SIDE 32767
+#define DEVO_ESIM_MAX_CROSSINGS 1048576
+#define DEVO_ESIM_MIN_THRESHOLD 1e-3
+enum { DEVO_ESIM_NONFINITE = 1, DEVO_ESIM_STAMPS = 2, DEVO_ESIM_SPAN = 4, DEVO_ESIM_CROSSINGS = 8 };
+int64_t devo_esim_max_span_ns(int H, int W);
+int devo_esim_count(const float* prev, const float* frames, const int64_t* prev_stamp, const int64_t* stamps, int T, int H, int W, const double* ref,
+                    const int64_t* last_t, double c_neg, double c_pos, int64_t refractory_ns, int64_t* counts, int64_t* status_span, devo_stream_t stream);
+int devo_esim_emit(const float* prev, const float* frames, const int64_t* prev_stamp, const int64_t* stamps, int T, int H, int W, const double* ref,
+                   const int64_t* last_t, double c_neg, double c_pos, int64_t refractory_ns, const int64_t* offsets, int64_t total, int64_t* keys,
+                   double* ref_out, int64_t* last_t_out, devo_stream_t stream);
+size_t devo_esim_sort_workspace_bytes(int64_t n, int H, int W, int64_t span_ns);
+int devo_esim_sort_keys(const int64_t* keys, int64_t* sorted, int64_t n, int H, int W, int64_t span_ns, void* ws, size_t ws_bytes, devo_stream_t stream);
+int devo_esim_decode(const int64_t* keys, int64_t n, int H, int W, const int64_t* first_stamp, int16_t* x, int16_t* y, int64_t* t, signed char* p,
+                     devo_stream_t stream);
+int devo_log_intensity(const unsigned char* images, int64_t n, const float* table, float* out, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
