@@ -16,6 +16,9 @@ undistorted frames (pinhole, radtan and equidistant models; what the reference o
 `simulate` makes the training data's events: contrast-threshold events from log-intensity frames (`ESIM`, the reference's esim_torch.ESIM),
 `log_intensity` in front of it and `frames_to_voxels` behind it (the loop of the reference's scripts/convert_tartan.py).
 
+`optim` is the tail of a training step: gradient-norm clip + AdamW in two launches (`AdamW`, a torch.optim.Optimizer that torch's own
+OneCycleLR drives and whose checkpoints are torch.optim.AdamW's).
+
 Importing this package does not load the HIP library; the first call into a backend does, and fails loudly
 if it is missing.  There is no CPU fallback anywhere in the package.
 """
@@ -23,7 +26,7 @@ __version__ = "0.1.0"
 
 
 def __getattr__(name):
-    if name in ("camera", "simulate"):                     # devo_amd.camera / devo_amd.simulate without an import of their own; loaded on first use
+    if name in ("camera", "simulate", "optim"):            # devo_amd.camera / .simulate / .optim without an import of their own; loaded on first use
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

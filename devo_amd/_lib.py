@@ -186,6 +186,13 @@ _SIGNATURES.update({
     "devo_esim_decode": [_vp, _i64, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "devo_log_intensity": [_vp, _i64, _vp, _vp, _vp],
 })
+_SIGNATURES.update({
+    "devo_optim_chunks": [_c_i64p, _i],
+    "devo_optim_moment_elems": [_c_i64p, _i],
+    "devo_optim_workspace_bytes": [],
+    "devo_optim_plan": [_c_i64p, _i, ctypes.POINTER(ctypes.c_int32), _c_i64p],
+    "devo_optim_step": [_vp, _i64, _vp, ctypes.POINTER(ctypes.c_void_p), _c_i64p, _i, _vp, _vp, _d, _d, _d, _d, _d, _d, _d, _d, _i, _vp, _vp, _vp, _sz, _vp],
+})
 for _n in ("exp", "log", "inv"):
     _SIGNATURES[f"devo_se3_{_n}"] = [_vp, _vp, _i64, _i, _vp]
     _SIGNATURES[f"devo_se3_{_n}_backward"] = [_vp, _vp, _vp, _i64, _i, _vp]
@@ -198,7 +205,8 @@ _RESTYPE = {"devo_last_error": ctypes.c_char_p, "devo_instnorm_workspace_bytes":
              "devo_voxel_hot_pixels_workspace_bytes": _sz, "devo_voxel_rescale_workspace_bytes": _sz, "devo_voxel_augment_workspace_bytes": _sz, "devo_depth_normalise_workspace_bytes": _sz, "devo_ba_workspace_bytes": _sz, "devo_neighbors_workspace_bytes": _sz,
              "devo_corr_backward_workspace_bytes": _sz, "devo_corr_patch_operand_bytes": _sz, "devo_upd_split_weight_bytes": _sz, "devo_upd_dw_workspace_bytes": _sz, "devo_upd_pack_weight_f16_bytes": _sz, "devo_upd_mlp2_weight_bytes": _sz, "devo_upd_rs_weight_bytes": _sz, "devo_upd_rs_split_weight_bytes": _sz, "devo_graph_workspace_bytes": _sz, "devo_loss_state_bytes": _sz,
              "devo_frame_complete_workspace_bytes": _sz, "devo_train_graph_workspace_bytes": _sz, "devo_frame_graph_workspace_bytes": _sz,
-             "devo_traj_eval_workspace_bytes": _sz, "devo_esim_max_span_ns": _i64, "devo_esim_sort_workspace_bytes": _sz}
+             "devo_traj_eval_workspace_bytes": _sz, "devo_esim_max_span_ns": _i64, "devo_esim_sort_workspace_bytes": _sz,
+             "devo_optim_chunks": _i64, "devo_optim_moment_elems": _i64, "devo_optim_workspace_bytes": _sz}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

@@ -988,6 +988,47 @@ Tensor log_intensity(const Tensor& images, const Tensor& table) {
   return out;
 }
 
+// ------------------------------------------------------------------------------------------------ optimiser step (devo_amd/optim.py; csrc/optim.hip)
+// Thin forms of the devo_optim_* entry points.  The Python module owns the tables, the moment buffers and every refusal that names a parameter;
+// the gradient addresses of a step arrive as integers (0: no gradient) and leave as kernel arguments.
+// sizes -> {chunk table int32 [chunks, 4], moment offsets int64 [n], elements of one moment buffer int64 [1]}, HOST tensors
+TensorList optim_plan(std::vector<int64_t> numel) {
+  TORCH_CHECK(!numel.empty() && numel.size() <= (size_t)DEVO_OPTIM_MAX_TENSORS, "optim.plan: ", numel.size(), " tensors (1 .. ", DEVO_OPTIM_MAX_TENSORS, ")");
+  const int n = (int)numel.size();
+  const int64_t chunks = devo_optim_chunks(numel.data(), n), elems = devo_optim_moment_elems(numel.data(), n);
+  TORCH_CHECK(chunks > 0 && elems > 0, "optim.plan: ", devo_last_error());
+  Tensor table = at::empty({chunks, 4}, at::TensorOptions().dtype(at::kInt)), offsets = at::empty({(int64_t)n}, at::TensorOptions().dtype(at::kLong));
+  check(devo_optim_plan(numel.data(), n, table.data_ptr<int32_t>(), offsets.data_ptr<int64_t>()), "optim.plan");
+  return {table, offsets, at::full({1}, elems, at::TensorOptions().dtype(at::kLong))};
+}
+
+void optim_step(const Tensor& chunk_table, const Tensor& tensor_table, std::vector<int64_t> grad_addrs, std::vector<int64_t> numel, Tensor& exp_avg, Tensor& exp_avg_sq,
+                double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double bc1, double bc2, bool skip_nonfinite, Tensor& counters,
+                Tensor& grad_norm, Tensor& workspace) {
+  require_gpu(chunk_table, tensor_table, exp_avg, exp_avg_sq, counters, grad_norm, workspace);
+  const int64_t n = (int64_t)numel.size();
+  TORCH_CHECK(n >= 1 && n <= DEVO_OPTIM_MAX_TENSORS && (int64_t)grad_addrs.size() == n, "optim.step: ", n, " sizes and ", grad_addrs.size(), " gradient addresses (1 .. ",
+              DEVO_OPTIM_MAX_TENSORS, " of each)");
+  const int64_t chunks = devo_optim_chunks(numel.data(), (int)n), elems = devo_optim_moment_elems(numel.data(), (int)n);
+  TORCH_CHECK(chunks > 0, "optim.step: ", devo_last_error());
+  TORCH_CHECK(chunk_table.scalar_type() == at::kInt && chunk_table.is_contiguous() && chunk_table.dim() == 2 && chunk_table.size(0) == chunks && chunk_table.size(1) == 4,
+              "optim.step: chunk_table must be the plan's contiguous int32 [", chunks, ", 4]");
+  TORCH_CHECK(tensor_table.scalar_type() == at::kLong && tensor_table.is_contiguous() && tensor_table.dim() == 2 && tensor_table.size(0) == n && tensor_table.size(1) == 2,
+              "optim.step: tensor_table must be a contiguous int64 [", n, ", 2]");
+  TORCH_CHECK(exp_avg.scalar_type() == at::kFloat && exp_avg.is_contiguous() && exp_avg.numel() == elems && exp_avg_sq.scalar_type() == at::kFloat &&
+              exp_avg_sq.is_contiguous() && exp_avg_sq.numel() == elems, "optim.step: the moment buffers must be contiguous float32 [", elems, "]");
+  TORCH_CHECK(counters.scalar_type() == at::kLong && counters.is_contiguous() && counters.numel() == 2 && grad_norm.scalar_type() == at::kDouble && grad_norm.numel() == 1 &&
+              workspace.scalar_type() == at::kByte && workspace.is_contiguous(), "optim.step: counters int64 [2], grad_norm float64 [1], workspace uint8");
+  for (const Tensor* t : {&tensor_table, (const Tensor*)&exp_avg, (const Tensor*)&exp_avg_sq, (const Tensor*)&counters, (const Tensor*)&grad_norm, (const Tensor*)&workspace})
+    TORCH_CHECK(t->device() == chunk_table.device(), "optim.step: tensors on different devices");
+  c10::DeviceGuard guard(chunk_table.device());
+  std::vector<const void*> grads((size_t)n);
+  for (int64_t i = 0; i < n; ++i) grads[(size_t)i] = (const void*)(intptr_t)grad_addrs[(size_t)i];
+  check(devo_optim_step(chunk_table.data_ptr<int32_t>(), chunks, tensor_table.data_ptr<int64_t>(), grads.data(), numel.data(), (int)n, exp_avg.data_ptr<float>(),
+                        exp_avg_sq.data_ptr<float>(), lr, beta1, beta2, eps, weight_decay, max_norm, bc1, bc2, skip_nonfinite ? 1 : 0, counters.data_ptr<int64_t>(),
+                        grad_norm.data_ptr<double>(), workspace.data_ptr(), (size_t)workspace.numel(), stream_of(chunk_table)), "optim.step");
+}
+
 // ------------------------------------------------------------------------------------------------ frame state (devo_amd/frames.py; csrc/frames.hip)
 // Thin forms of the devo_frame_* entry points.  `status` is a pinned HOST tensor the kernels write (devo_hip.h); the Python module checks
 // shapes, owns the log and the workspace and reads the status.
@@ -1158,6 +1199,9 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("esim_sort(Tensor keys, int H, int W, int span_ns) -> Tensor");
   m.def("esim_decode(Tensor keys, int H, int W, Tensor first_stamp) -> Tensor[]");
   m.def("log_intensity(Tensor images, Tensor table) -> Tensor");
+  m.def("optim_plan(int[] numel) -> Tensor[]");
+  m.def("optim_step(Tensor chunk_table, Tensor tensor_table, int[] grad_addrs, int[] numel, Tensor(a!) exp_avg, Tensor(b!) exp_avg_sq, float lr, float beta1, float beta2, "
+        "float eps, float weight_decay, float max_norm, float bc1, float bc2, bool skip_nonfinite, Tensor(c!) counters, Tensor(d!) grad_norm, Tensor(e!) workspace) -> ()");
 }
 TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("corr_forward", &corr_forward);
@@ -1189,6 +1233,8 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("esim_sort", &esim_sort);
   m.impl("esim_decode", &esim_decode);
   m.impl("log_intensity", &log_intensity);
+  m.impl("optim_plan", &optim_plan);
+  m.impl("optim_step", &optim_step);
 }
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -1271,6 +1317,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   sim.def("decode", &esim_decode);
   sim.def("log_intensity", &log_intensity);
   sim.def("max_span_ns", [](int64_t H, int64_t W) { return (H > INT32_MAX || W > INT32_MAX) ? (int64_t)0 : devo_esim_max_span_ns((int)H, (int)W); });
+  auto opt = m.def_submodule("optim", "devo_amd.optim: gradient-norm clip + AdamW in two launches (the reference's train.py:248-249)");
+  opt.def("plan", &optim_plan);
+  opt.def("step", &optim_step);
+  opt.def("workspace_bytes", []() { return (int64_t)devo_optim_workspace_bytes(); });
+  opt.attr("CHUNK") = (int64_t)DEVO_OPTIM_CHUNK;
   auto fr = m.def_submodule("frames", "devo_amd.frames: devo/devo.py:179-196, :276-280, :342-344, :487-520, :534 on the GPU");
   fr.def("begin_frame", &fr_begin);
   fr.def("point_cloud", &fr_point_cloud);

@@ -264,9 +264,13 @@ def make_batch(workload="cfg2_m80", seed=1234, device="cuda"):
                 ii=d(ii), jj=d(jj), kk=d(kk), H=H, W=W, R=R, n=n, M=M, E=int(ii.numel()))
 
 
-def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", randaug=False):
+def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", randaug=False, optimizer="torch", total_steps=None, clip=10.0):
     """net (DDP-wrapped when world_size > 1, train.py:106-107; ddp=True: also at world size 1, given a process group), AdamW (train.py:109).
-    norm, randaug: TrainNet's."""
+    norm, randaug: TrainNet's.  optimizer: "torch" (torch.optim.AdamW; train_step clips in front of it) or "fused" (devo_amd.optim.AdamW with
+    max_norm = clip: clip and step in two launches).  total_steps: also build the reference's OneCycleLR (train.py:110-111) and return it as a
+    fourth value."""
+    if optimizer not in ("torch", "fused"):
+        raise ValueError(f"build_trainer: optimizer {optimizer!r} (torch or fused)")
     torch.manual_seed(seed)                                   # identical initial weights on every rank (train.py:41)
     net = TrainNet(norm=norm, randaug=randaug).to(device).train()
     model = net
@@ -274,16 +278,57 @@ def build_trainer(device, world_size, lr=8e-5, seed=0, ddp=None, norm="none", ra
         from torch.nn.parallel import DistributedDataParallel as DDP
         dev = torch.device(device)
         model = DDP(net, device_ids=[dev.index] if dev.type == "cuda" else None, find_unused_parameters=False)
-    opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=1e-6)
-    return net, model, opt
+    if optimizer == "fused":
+        from . import optim
+        named = list(model.named_parameters())
+        opt = optim.AdamW([q for _, q in named], lr=lr, weight_decay=1e-6, max_norm=clip, names=[k for k, _ in named])
+    else:
+        opt = torch.optim.AdamW(model.parameters(), lr=lr, weight_decay=1e-6)
+    if total_steps is None:
+        return net, model, opt
+    from . import optim
+    return net, model, opt, optim.one_cycle(opt, lr, total_steps)
 
 
-def train_step(model, opt, batch, iters=18, clip=10.0, objective="bench", schedule="full", **schedule_args):
-    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step (train.py:166-250).  objective, schedule
-    (and init_frames / warmup through schedule_args): TrainNet.forward's."""
+def train_step(model, opt, batch, iters=18, clip=10.0, objective="bench", schedule="full", scheduler=None, **schedule_args):
+    """optimizer.zero_grad -> forward -> backward (DDP: gradient all-reduce) -> clip -> step -> scheduler.step (train.py:166-250).  An
+    optimiser that clips itself (devo_amd.optim.AdamW with max_norm) is not clipped for again.  objective, schedule (and init_frames / warmup
+    through schedule_args): TrainNet.forward's."""
     opt.zero_grad(set_to_none=True)
     loss = model(batch, iters=iters, objective=objective, schedule=schedule, **schedule_args)
     loss.backward()
-    torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
+    if getattr(opt, "max_norm", None) is None:
+        torch.nn.utils.clip_grad_norm_(model.parameters(), clip)
     opt.step()
+    if scheduler is not None:
+        scheduler.step()
     return loss.detach()
+
+
+def save_checkpoint(path, steps, model, opt, scheduler=None):
+    """train.py:275-280: {'steps', 'model_state_dict' (of the bare module under DDP), 'optimizer_state_dict', 'scheduler_state_dict'}.  Either
+    optimiser writes torch.optim.AdamW's format, so a checkpoint of one resumes in the other."""
+    net = model.module if hasattr(model, "module") else model
+    ckpt = {"steps": int(steps), "model_state_dict": net.state_dict(), "optimizer_state_dict": opt.state_dict()}
+    if scheduler is not None:
+        ckpt["scheduler_state_dict"] = scheduler.state_dict()
+    torch.save(ckpt, path)
+
+
+def load_checkpoint(path, model, opt=None, scheduler=None):
+    """train.py:114-138 -> the checkpoint's step count (0 when it has none).  A checkpoint without 'model_state_dict' is the legacy form, a
+    bare state dict: 'module.' is stripped from its keys and only entries whose name and shape match the model are taken (train.py:120-132)."""
+    ckpt = torch.load(path)
+    net = model.module if hasattr(model, "module") else model
+    if "model_state_dict" in ckpt:
+        net.load_state_dict(ckpt["model_state_dict"])
+    else:
+        have = net.state_dict()
+        renamed = {k.replace("module.", ""): v for k, v in ckpt.items()}
+        have.update({k: v for k, v in renamed.items() if k in have and have[k].shape == v.shape})
+        net.load_state_dict(have, strict=False)
+    if opt is not None and "optimizer_state_dict" in ckpt:
+        opt.load_state_dict(ckpt["optimizer_state_dict"])
+    if scheduler is not None and "scheduler_state_dict" in ckpt:
+        scheduler.load_state_dict(ckpt["scheduler_state_dict"])
+    return int(ckpt["steps"]) if "steps" in ckpt else 0

@@ -41,7 +41,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   devo_frame_graph_distances, devo_frame_graph_lists, devo_frame_graph_workspace_bytes; and devo_patch_select; and devo_traj_eval,
                                   devo_traj_eval_workspace_bytes; and devo_camera_undistort_points, devo_camera_distort_points, devo_image_remap;
                                   and devo_esim_count, devo_esim_emit, devo_esim_sort_keys, devo_esim_sort_workspace_bytes, devo_esim_decode, devo_esim_max_span_ns,
-                                  devo_log_intensity);
+                                  devo_log_intensity; and devo_optim_chunks, devo_optim_moment_elems, devo_optim_workspace_bytes, devo_optim_plan,
+                                  devo_optim_step);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -1016,6 +1017,48 @@ int devo_esim_sort_keys(const int64_t* keys, int64_t* sorted, int64_t n, int H, 
 int devo_esim_decode(const int64_t* keys, int64_t n, int H, int W, const int64_t* first_stamp, int16_t* x, int16_t* y, int64_t* t, signed char* p,
                      devo_stream_t stream);
 int devo_log_intensity(const unsigned char* images, int64_t n, const float* table, float* out, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Optimiser step: gradient-norm clip + AdamW over a list of fp32 tensors (what the reference's train.py:248-249 does with clip_grad_norm_(10)
+ * and torch.optim.AdamW.step(); csrc/optim.hip; devo_amd/optim.py).  Tensor t has numel[t] elements that lie DENSE in memory from its address
+ * on (any permutation of a contiguous layout; parameter and gradient in the same one), 1 <= numel[t] < 2^31, at most DEVO_OPTIM_MAX_TENSORS
+ * tensors.  Every tensor is cut into chunks of DEVO_OPTIM_CHUNK elements.
+ *   devo_optim_chunks         the number of chunks of the list (0: refused sizes).
+ *   devo_optim_moment_elems   the elements of each of the two flat moment buffers: every tensor's slice is padded to a multiple of 4 elements,
+ *                             so each starts on a 16-byte boundary (0: refused sizes).
+ *   devo_optim_plan           HOST outputs, built once: chunk_table [chunks, 4] int32 = (tensor, element offset (uint32), length, 0) in tensor
+ *                             order, and moment_offsets [n_tensors] = the element offset of every tensor's slice in the moment buffers.
+ *   devo_optim_workspace_bytes  the bytes of the step's workspace (the norm's partial sums).
+ *   devo_optim_step           one step.  DEVICE pointers: chunk_table (the plan's, uploaded), tensor_table [n_tensors, 2] int64 = (parameter
+ *                             address, moment offset), exp_avg, exp_avg_sq, counters, grad_norm, workspace.  HOST pointers: grads [n_tensors]
+ *                             (this step's gradient addresses; NULL: the tensor has no gradient and is skipped whole, parameter and moments
+ *                             untouched) and numel [n_tensors].  The gradient addresses travel as kernel arguments, DEVO_OPTIM_GROUP tensors
+ *                             per launch, so a step may be enqueued before the one before it has run; nothing is synchronised or copied.
+ *     launch 1   sum of g^2 in fp64 (every g widened first), one partial per workgroup, no atomics: bit-reproducible.
+ *     launch 2   every workgroup sums the partials in one fixed order; norm = sqrt(sum) -> *grad_norm (fp64, BEFORE clipping);
+ *                coef = max_norm < 0 ? 1 : min(1, max_norm / (norm + 1e-6)); then per element in fp32, one rounding per operation:
+ *                  g = g coef;  p = p (1 - lr wd);  m = m + (g - m)(1 - beta1);  v = v beta2 + ((1 - beta2) g) g;
+ *                  p = p + (-(lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps)
+ *                (torch.optim.AdamW's single-tensor form; lr / bc1, sqrt(bc2), 1 - lr wd, 1 - beta formed in fp64 and rounded to fp32).
+ *                Gradients are read, never written.  bc1 = 1 - beta1^t and bc2 = 1 - beta2^t are the caller's.
+ *     skip_nonfinite = 1   a step whose norm is inf or NaN writes nothing to p, m, v; a third launch then adds 1 to counters[0] (applied)
+ *                or counters[1] (skipped), int64 [2]; bc1 and bc2 are formed on the device from t = counters[0] + 1 and the arguments are ignored.
+ *                With 0, non-finite values propagate as in torch and counters may be NULL.
+ * Refused with DEVO_ERR_ARG before any launch: null or misaligned pointers (16 bytes for tables, moments and gradients), sizes outside the
+ * limits, n_chunks that is not the list's, lr / eps / weight_decay negative or not finite, betas outside [0, 1), a NaN max_norm, bias
+ * corrections outside (0, 1], a workspace that is too small.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_OPTIM_CHUNK 2048
+#define DEVO_OPTIM_GROUP 256
+#define DEVO_OPTIM_MAX_TENSORS 4096
+#define DEVO_OPTIM_MAX_PARTIALS 2048
+int64_t devo_optim_chunks(const int64_t* numel, int n_tensors);
+int64_t devo_optim_moment_elems(const int64_t* numel, int n_tensors);
+size_t devo_optim_workspace_bytes(void);
+int devo_optim_plan(const int64_t* numel, int n_tensors, int32_t* chunk_table, int64_t* moment_offsets);
+int devo_optim_step(const int32_t* chunk_table, int64_t n_chunks, const int64_t* tensor_table, const void* const* grads, const int64_t* numel, int n_tensors,
+                    float* exp_avg, float* exp_avg_sq, double lr, double beta1, double beta2, double eps, double weight_decay, double max_norm, double bc1,
+                    double bc2, int skip_nonfinite, int64_t* counters, double* grad_norm, void* workspace, size_t workspace_bytes, devo_stream_t stream);
 
 #ifdef __cplusplus
 }
