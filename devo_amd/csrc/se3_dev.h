@@ -8,8 +8,10 @@
 namespace devo {
 
 template <typename T> struct Consts;
-template <> struct Consts<float>  { static constexpr float  eps = 1e-6f; };
-template <> struct Consts<double> { static constexpr double eps = 1e-6;  };
+// eps: the reference's small-angle switch (common.h:7), kept for so3_exp / so3_log, whose forms do not cancel.
+// series_max: below it the Jacobian coefficients come from their power series (jc_* below), above it from the closed forms.
+template <> struct Consts<float>  { static constexpr float  eps = 1e-6f; static constexpr float  series_max = 1.0f; };
+template <> struct Consts<double> { static constexpr double eps = 1e-6;  static constexpr double series_max = 0.3;  };
 
 #define DEVO_HD __device__ __forceinline__
 
@@ -175,20 +177,48 @@ template <typename T> DEVO_HD V3<T> so3_log(Q4<T> q) {                     // so
   }
   return {f * q.x, f * q.y, f * q.z};
 }
+// The Jacobian coefficients.  Their closed forms subtract nearly equal numbers for small theta — (1 - cos t)/t^2 keeps
+// about eps_machine / t^2 — so below Consts<T>::series_max each is a six-term Horner series in theta^2 (truncation below
+// 1e-17 at 0.3 and below 1e-10 at 1.0), exact down to theta = 0: no separate eps branch.  A deliberate departure from the
+// reference's single switch at 1e-6 ("small-angle Jacobians").
+template <typename T> DEVO_HD T horner6(T x, T k0, T k1, T k2, T k3, T k4, T k5) {
+  return k0 + x * (k1 + x * (k2 + x * (k3 + x * (k4 + x * k5))));
+}
+template <typename T> DEVO_HD T jc_one_minus_cos(T theta2, T theta) {      // (1 - cos t) / t^2 = sum (-1)^k t^2k / (2k+2)!
+  if (theta < Consts<T>::series_max)
+    return horner6<T>(theta2, T(1.0 / 2.0), T(-1.0 / 24.0), T(1.0 / 720.0), T(-1.0 / 40320.0), T(1.0 / 3628800.0), T(-1.0 / 479001600.0));
+  return (T(1) - t_cos<T>(theta)) / theta2;
+}
+template <typename T> DEVO_HD T jc_t_minus_sin(T theta2, T theta) {        // (t - sin t) / t^3 = sum (-1)^k t^2k / (2k+3)!
+  if (theta < Consts<T>::series_max)
+    return horner6<T>(theta2, T(1.0 / 6.0), T(-1.0 / 120.0), T(1.0 / 5040.0), T(-1.0 / 362880.0), T(1.0 / 39916800.0), T(-1.0 / 6227020800.0));
+  return (theta - t_sin<T>(theta)) / (theta2 * theta);
+}
+template <typename T> DEVO_HD T jc_q2(T theta2, T theta) {                 // (t^2 + 2 cos t - 2) / (2 t^4) = sum (-1)^k t^2k / (2k+4)!
+  if (theta < Consts<T>::series_max)
+    return horner6<T>(theta2, T(1.0 / 24.0), T(-1.0 / 720.0), T(1.0 / 40320.0), T(-1.0 / 3628800.0), T(1.0 / 479001600.0), T(-1.0 / 87178291200.0));
+  return (theta2 + 2 * t_cos<T>(theta) - 2) / (2 * theta2 * theta2);
+}
+template <typename T> DEVO_HD T jc_q3(T theta2, T theta) {                 // (2t - 3 sin t + t cos t) / (2 t^5) = sum (-1)^k (k+1) t^2k / (2k+5)!
+  if (theta < Consts<T>::series_max)
+    return horner6<T>(theta2, T(1.0 / 120.0), T(-1.0 / 2520.0), T(1.0 / 120960.0), T(-1.0 / 9979200.0), T(1.0 / 1245404160.0), T(-1.0 / 217945728000.0));
+  return (2 * theta - 3 * t_sin<T>(theta) + theta * t_cos<T>(theta)) / (2 * theta2 * theta2 * theta);
+}
+template <typename T> DEVO_HD T jc_inv(T theta2, T theta) {                // (1 - (t/2) cot(t/2)) / t^2 = sum |B_2k| t^(2k-2) / (2k)!, k >= 1
+  if (theta < Consts<T>::series_max)
+    return horner6<T>(theta2, T(1.0 / 12.0), T(1.0 / 720.0), T(1.0 / 30240.0), T(1.0 / 1209600.0), T(1.0 / 47900160.0), T(691.0 / 1307674368000.0));
+  T half = T(0.5) * theta;
+  return (T(1) - theta * t_cos<T>(half) / (T(2) * t_sin<T>(half))) / theta2;
+}
 template <typename T> DEVO_HD M3<T> so3_left_jacobian(V3<T> phi) {         // so3.h:170-187
   M3<T> P = hat(phi), P2 = mm(P, P);
   T theta2 = dot(phi, phi), theta = t_sqrt<T>(theta2);
-  bool small = theta < Consts<T>::eps;
-  T c1 = small ? T(0.5) - T(1.0 / 24.0) * theta2 : (T(1) - t_cos<T>(theta)) / theta2;
-  T c2 = small ? T(1.0 / 6.0) - T(1.0 / 120.0) * theta2 : (theta - t_sin<T>(theta)) / (theta2 * theta);
-  return lin3(c1, P, c2, P2);
+  return lin3(jc_one_minus_cos<T>(theta2, theta), P, jc_t_minus_sin<T>(theta2, theta), P2);
 }
 template <typename T> DEVO_HD M3<T> so3_left_jacobian_inverse(V3<T> phi) { // so3.h:189-205
   M3<T> P = hat(phi), P2 = mm(P, P);
-  T theta2 = dot(phi, phi), theta = t_sqrt<T>(theta2), half = T(0.5) * theta;
-  T c2 = (theta < Consts<T>::eps) ? T(1.0 / 12.0)
-         : (T(1) - theta * t_cos<T>(half) / (T(2) * t_sin<T>(half))) / (theta * theta);
-  return lin3(T(-0.5), P, c2, P2);
+  T theta2 = dot(phi, phi), theta = t_sqrt<T>(theta2);
+  return lin3(T(-0.5), P, jc_inv<T>(theta2, theta), P2);
 }
 template <typename T> DEVO_HD SE3<T> se3_exp(const T* a) {                 // se3.h:134-142
   V3<T> tau{a[0], a[1], a[2]}, phi{a[3], a[4], a[5]};
@@ -205,12 +235,8 @@ template <typename T> DEVO_HD void se3_log(const SE3<T>& X, T* a) {        // se
 template <typename T> DEVO_HD M3<T> se3_calcQ(const T* a) {                // se3.h:144-173
   V3<T> tau{a[0], a[1], a[2]}, phi{a[3], a[4], a[5]};
   M3<T> Tau = hat(tau), Phi = hat(phi);
-  T theta2 = dot(phi, phi), theta = t_sqrt<T>(theta2), theta4 = theta2 * theta2;
-  bool small = theta < Consts<T>::eps;
-  T c1 = small ? T(1.0 / 6.0) - T(1.0 / 120.0) * theta2 : (theta - t_sin<T>(theta)) / (theta2 * theta);
-  T c2 = small ? T(1.0 / 24.0) - T(1.0 / 720.0) * theta2 : (theta2 + 2 * t_cos<T>(theta) - 2) / (2 * theta4);
-  T c3 = small ? T(1.0 / 120.0) - T(1.0 / 2520.0) * theta2
-               : (2 * theta - 3 * t_sin<T>(theta) + theta * t_cos<T>(theta)) / (2 * theta4 * theta);
+  T theta2 = dot(phi, phi), theta = t_sqrt<T>(theta2);
+  T c1 = jc_t_minus_sin<T>(theta2, theta), c2 = jc_q2<T>(theta2, theta), c3 = jc_q3<T>(theta2, theta);
   M3<T> PT = mm(Phi, Tau), TP = mm(Tau, Phi), PTP = mm(PT, Phi);
   M3<T> PPT = mm(Phi, PT), TPP = mm(TP, Phi), PTPP = mm(PTP, Phi), PPTP = mm(Phi, PTP);
   M3<T> Q;

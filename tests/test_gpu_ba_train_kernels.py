@@ -273,7 +273,13 @@ def _apply_inputs(N, fixedp, n_opt, Np=300, P=3):
         dX[:, :3] = 0.1 * torch.randn(n_opt, 3, generator=g)
         phi = torch.randn(n_opt, 3, generator=g)
         dX[:, 3:] = phi / phi.norm(dim=-1, keepdim=True) * (0.05 + 0.45 * torch.rand(n_opt, 1, generator=g))
-        dX[::3, 3:] = 0.0                                               # rotations exactly zero, or |phi| >= 0.05
+        # |phi| cycles through exactly zero, the band where the closed-form Jacobian coefficients cancel (3e-6 ... 1e-2), and the random 0.05 .. 0.5
+        # (None: the random magnitude stays).  In-band rows get translations of order one: the coefficients' error enters g_dX times |tau|
+        band = [0.0, None, 1e-3, 3e-6, 1e-4, 1e-2, None, None, None]
+        for i in range(n_opt):
+            if band[i % len(band)] is not None:
+                dX[i, 3:] *= band[i % len(band)] / dX[i, 3:].norm()
+                dX[i, :3] *= 10.0
     g_poses = torch.cat([torch.randn(1, N, 6, generator=g), torch.zeros(1, N, 1)], -1).contiguous()      # lietorch: a tangent in six of seven slots
     g_patches = torch.randn(1, Np, 3, P, P, generator=g)
     return poses, patches, dX.reshape(-1), dZ, g_poses, g_patches
@@ -287,12 +293,12 @@ def _apply_ref(poses, patches, dX, dZ, fixedp, n_opt, g_poses, g_patches):
     return po.detach(), qo.detach(), torch.autograd.grad(loss, leaves)
 
 
-@pytest.mark.parametrize("N,fixedp,n_opt", [(5, 1, 4), (5, 2, 2), (6, 0, 6), (4, 1, 0)])
+@pytest.mark.parametrize("N,fixedp,n_opt", [(5, 1, 4), (5, 2, 2), (6, 0, 6), (4, 1, 0), (10, 1, 9)])
 def test_apply_step_and_adjoint_against_the_reference(N, fixedp, n_opt):
     """devo_ba_apply_step / _backward through the C interface (n_opt = 0: dX = NULL).  300 patches: N + Np crosses a workgroup.  Quaternions partly
     un-normalised.  The clamp [0.25, 8]: a depth that lands exactly on a bound passes its gradient (ATen's inclusive mask), one ulp outside does not.
-    A missing cotangent (NULL) contributes zero; the seventh slot of every pose gradient is 0.  Rotations of dX are exactly zero or at least 0.05:
-    in the fp32 band 1e-6 < |phi| < 1e-2 the coefficient (1 - cos t) / t^2 cancels, as in the reference's own float kernels — out of scope here.
+    A missing cotangent (NULL) contributes zero; the seventh slot of every pose gradient is 0.  Rotations of dX are exactly zero, in the band
+    3e-6 .. 1e-2 where the closed form of (1 - cos t) / t^2 cancels in fp32 (nine optimised poses reach every magnitude), or between 0.05 and 0.5.
     Tolerance: 2e-5 of each tensor's scale, the figure tests/test_gpu_lietorch.py uses for the same group operations."""
     from devo_amd import _lib as L
     poses, patches, dX, dZ, g_poses, g_patches = _apply_inputs(N, fixedp, n_opt)
