@@ -1123,7 +1123,7 @@ int devo_upd_softagg_hint(const void* f, const void* g, int64_t ld_fg, const int
   DEVO_REQUIRE(((reinterpret_cast<uintptr_t>(f) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(y)) & 7) == 0, "devo_upd_softagg: operands must be 8-byte aligned");
   if (E == 0) return DEVO_OK;
   hipStream_t st_ = (hipStream_t)stream;
-  if (upd_vec_ok(dtype, E, dim, {f, g}, {ld_fg}) && dim / (dtype == DEVO_F32 ? 4 : 8) <= 128) {
+  if (upd_vec_ok(dtype, E, dim, {f, g, y}, {ld_fg}) && dim / (dtype == DEVO_F32 ? 4 : 8) <= 128) {      // (y: k_softagg_w stores 16-byte chunks)
     const int cpr = dim / (dtype == DEVO_F32 ? 4 : 8);
     // one workgroup per group: the caller's estimate sizes the grid (a workgroup without a group still has to be placed, read the count and
     // retire: with E workgroups — 4 096 here — for 225 frame pairs the launch was eight rounds of empty 1 024-thread workgroups); the
