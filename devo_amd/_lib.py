@@ -201,6 +201,10 @@ for _n in ("mul", "adj", "adjT", "act", "act4"):
     _SIGNATURES[f"devo_se3_{_n}_backward"] = [_vp, _vp, _vp, _vp, _vp, _i64, _i, _vp]
 _SIGNATURES["devo_se3_as_matrix"] = [_vp, _vp, _i64, _i, _vp]
 _SIGNATURES["devo_se3_jinv"] = [_vp, _vp, _vp, _i64, _i, _vp]
+# the same calls for every group (1 SO3, 2 RxSO3, 3 SE3, 4 Sim3): the group id in front
+for _n in [k for k in _SIGNATURES if k.startswith("devo_se3_")]:
+    _SIGNATURES["devo_lie_" + _n[len("devo_se3_"):]] = [_i] + _SIGNATURES[_n]
+_SIGNATURES["devo_lie_projector"] = [_i, _vp, _vp, _i64, _i, _vp]
 _RESTYPE = {"devo_last_error": ctypes.c_char_p, "devo_instnorm_workspace_bytes": _sz, "devo_voxel_std_workspace_bytes": _sz, "devo_voxelize_windows_workspace_bytes": _sz,
              "devo_voxel_hot_pixels_workspace_bytes": _sz, "devo_voxel_rescale_workspace_bytes": _sz, "devo_voxel_augment_workspace_bytes": _sz, "devo_depth_normalise_workspace_bytes": _sz, "devo_ba_workspace_bytes": _sz, "devo_neighbors_workspace_bytes": _sz,
              "devo_corr_backward_workspace_bytes": _sz, "devo_corr_patch_operand_bytes": _sz, "devo_upd_split_weight_bytes": _sz, "devo_upd_dw_workspace_bytes": _sz, "devo_upd_pack_weight_f16_bytes": _sz, "devo_upd_mlp2_weight_bytes": _sz, "devo_upd_rs_weight_bytes": _sz, "devo_upd_rs_split_weight_bytes": _sz, "devo_graph_workspace_bytes": _sz, "devo_loss_state_bytes": _sz,

@@ -545,65 +545,78 @@ Tensor ba_transform(Tensor poses_, Tensor patches_, Tensor intrinsics_, Tensor i
   return c;
 }
 
-// ------------------------------------------------------------------------------------------------ lietorch_backends (lietorch.cpp:286-316), SE3 only
-constexpr int64_t SE3_ID = 3;
-template <typename... Ts>
-void lie_chk(int64_t group_id, const Tensor& first, const Ts&... rest) {
-  TORCH_CHECK(group_id == SE3_ID, "lietorch_backends (devo_amd): only SE3 (group_id 3) is implemented, got ", group_id);
-  for (const Tensor* t : {&first, &rest...}) {
+// ------------------------------------------------------------------------------------------------ lietorch_backends (lietorch.cpp:286-316): SO3, RxSO3, SE3, Sim3
+// Operand kinds: the last dimension of every operand is checked against the group (the reference reads whatever is there).
+enum LieDim { LIE_N = -1, LIE_K = -2 };   // an element (N), a tangent (K); 3 and 4 stand for themselves (points)
+inline int64_t lie_dim(int64_t group_id, int what) {
+  static const int64_t N[5] = {0, 4, 5, 7, 8};                                                         // dispatch.h, so3.h:14-15 ... sim3.h:19-20
+  return what == LIE_N ? N[group_id] : what == LIE_K ? N[group_id] - 1 : what;
+}
+inline void lie_chk(int64_t group_id, std::initializer_list<std::pair<const Tensor*, int>> ts) {
+  TORCH_CHECK(group_id >= 1 && group_id <= 4, "lietorch_backends (devo_amd): group_id must be 1 (SO3), 2 (RxSO3), 3 (SE3) or 4 (Sim3), got ", group_id);
+  const Tensor& first = *ts.begin()->first;
+  for (const auto& tw : ts) {
+    const Tensor* t = tw.first;
     TORCH_CHECK(t->is_cuda(), "devo_amd: tensors must live on the GPU (the HIP path has no CPU fallback)");
     TORCH_CHECK(t->is_contiguous(), "lietorch_backends: input must be contiguous");                    // lietorch.cpp:7
     TORCH_CHECK(t->scalar_type() == at::kFloat || t->scalar_type() == at::kDouble, "lietorch_backends: float32/float64 only, got ", t->scalar_type());
     TORCH_CHECK(t->scalar_type() == first.scalar_type(), "lietorch_backends: mixed dtypes");
+    const int64_t want = lie_dim(group_id, tw.second);
+    TORCH_CHECK(t->dim() >= 2 && t->size(-1) == want && t->size(0) == first.size(0) && t->numel() == t->size(0) * want, "lietorch_backends: expected a [", first.size(0),
+                ", ", want, "] tensor for group ", group_id, ", got ", t->sizes());
   }
 }
-typedef int (*un_fn)(const void*, void*, int64_t, int, devo_stream_t);
-typedef int (*unb_fn)(const void*, const void*, void*, int64_t, int, devo_stream_t);
-typedef int (*bin_fn)(const void*, const void*, void*, int64_t, int, devo_stream_t);
-typedef int (*binb_fn)(const void*, const void*, const void*, void*, void*, int64_t, int, devo_stream_t);
+typedef int (*un_fn)(int, const void*, void*, int64_t, int, devo_stream_t);
+typedef int (*unb_fn)(int, const void*, const void*, void*, int64_t, int, devo_stream_t);
+typedef int (*bin_fn)(int, const void*, const void*, void*, int64_t, int, devo_stream_t);
+typedef int (*binb_fn)(int, const void*, const void*, const void*, void*, void*, int64_t, int, devo_stream_t);
 
-template <un_fn F, int OUT>
+template <un_fn F, int IN, int OUT>
 Tensor lie_unary(int64_t gid, Tensor X) {
-  lie_chk(gid, X);
+  lie_chk(gid, {{&X, IN}});
   c10::DeviceGuard guard(X.device());
-  Tensor out = at::empty({X.size(0), OUT}, X.options());
-  check(F(X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
+  Tensor out = at::empty({X.size(0), lie_dim(gid, OUT)}, X.options());
+  check(F((int)gid, X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
   return out;
 }
-template <unb_fn F, int OUT>
+template <unb_fn F, int GRAD, int IN, int OUT>
 TensorList lie_unary_bwd(int64_t gid, Tensor grad, Tensor X) {
-  lie_chk(gid, grad, X);
+  lie_chk(gid, {{&grad, GRAD}, {&X, IN}});
   c10::DeviceGuard guard(X.device());
-  Tensor out = at::empty({X.size(0), OUT}, X.options());
-  check(F(grad.data_ptr(), X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
+  Tensor out = at::empty({X.size(0), lie_dim(gid, OUT)}, X.options());
+  check(F((int)gid, grad.data_ptr(), X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
   return {out};
 }
-template <bin_fn F, int OUT>
+template <bin_fn F, int Y, int OUT>
 Tensor lie_binary(int64_t gid, Tensor X, Tensor y) {
-  lie_chk(gid, X, y);
+  lie_chk(gid, {{&X, LIE_N}, {&y, Y}});
   c10::DeviceGuard guard(X.device());
-  Tensor out = at::empty({X.size(0), OUT}, X.options());
-  check(F(X.data_ptr(), y.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
+  Tensor out = at::empty({X.size(0), lie_dim(gid, OUT)}, X.options());
+  check(F((int)gid, X.data_ptr(), y.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
   return out;
 }
-template <binb_fn F, int DY>
+template <binb_fn F, int GRAD, int Y>
 TensorList lie_binary_bwd(int64_t gid, Tensor grad, Tensor X, Tensor y) {
-  lie_chk(gid, grad, X, y);
+  lie_chk(gid, {{&grad, GRAD}, {&X, LIE_N}, {&y, Y}});
   c10::DeviceGuard guard(X.device());
-  Tensor dX = at::empty({X.size(0), 7}, X.options()), dy = at::empty({X.size(0), DY}, X.options());
-  check(F(grad.data_ptr(), X.data_ptr(), y.data_ptr(), dX.data_ptr(), dy.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
+  Tensor dX = at::empty({X.size(0), lie_dim(gid, LIE_N)}, X.options()), dy = at::empty({X.size(0), lie_dim(gid, Y)}, X.options());
+  check(F((int)gid, grad.data_ptr(), X.data_ptr(), y.data_ptr(), dX.data_ptr(), dy.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "lietorch_backends");
   return {dX, dy};
 }
 Tensor lie_as_matrix(int64_t gid, Tensor X) {
-  lie_chk(gid, X);
+  lie_chk(gid, {{&X, LIE_N}});
   c10::DeviceGuard guard(X.device());
   Tensor out = at::empty({X.size(0), 4, 4}, X.options());
-  check(devo_se3_as_matrix(X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "devo_se3_as_matrix");
+  check(devo_lie_as_matrix((int)gid, X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "devo_lie_as_matrix");
   return out;
 }
-Tensor lie_projector(int64_t, Tensor) {
-  TORCH_CHECK(false, "lietorch_backends.projector (ToVec/FromVec) is outside the DEVO hot path (SURVEY.md §2.1 row 3): never reached from devo.py / enet.py / train.py");
-  return Tensor();
+Tensor lie_projector(int64_t gid, Tensor X) {                                                          // lietorch.cpp:312: [n, N, N]
+  lie_chk(gid, {{&X, LIE_N}});
+  c10::DeviceGuard guard(X.device());
+  const int64_t N = lie_dim(gid, LIE_N);
+  Tensor out = at::empty({X.size(0), N, N}, X.options());
+  check(devo_lie_projector((int)gid, X.data_ptr(), out.data_ptr(), X.size(0), dtype_code(X), stream_of(X)), "devo_lie_projector");
+  return out;
 }
 
 // extras for devo_amd.backends.cuda_corr (one cache for both bindings)
@@ -1179,6 +1192,7 @@ TORCH_LIBRARY(devo_hip, m) {
   m.def("se3_adjT(int group_id, Tensor X, Tensor a) -> Tensor");
   m.def("se3_act(int group_id, Tensor X, Tensor p) -> Tensor");
   m.def("se3_act4(int group_id, Tensor X, Tensor p) -> Tensor");
+  m.def("se3_projector(int group_id, Tensor X) -> Tensor");
   m.def("loss_forward(Tensor x, Tensor y, Tensor v, Tensor Gs, Tensor Ps, Tensor? scores, Tensor? v_full, Tensor? x_full, Tensor? y_full, Tensor? ba_weights, Tensor? kk, "
         "bool deterministic, float flow_weight, float pose_weight, float scores_weight, bool use_pose) -> Tensor[]");
   m.def("loss_backward(Tensor g, Tensor state, int Ec, int P, int n, int Ef, int n_patches, float flow_weight, float pose_weight, float scores_weight, bool need_coords, "
@@ -1211,14 +1225,15 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("ba_forward", &ba_forward_op);
   m.impl("ba_neighbors", &ba_neighbors);
   m.impl("ba_reproject", &ba_reproject);
-  m.impl("se3_exp", &lie_unary<devo_se3_exp, 7>);
-  m.impl("se3_log", &lie_unary<devo_se3_log, 6>);
-  m.impl("se3_inv", &lie_unary<devo_se3_inv, 7>);
-  m.impl("se3_mul", &lie_binary<devo_se3_mul, 7>);
-  m.impl("se3_adj", &lie_binary<devo_se3_adj, 6>);
-  m.impl("se3_adjT", &lie_binary<devo_se3_adjT, 6>);
-  m.impl("se3_act", &lie_binary<devo_se3_act, 3>);
-  m.impl("se3_act4", &lie_binary<devo_se3_act4, 4>);
+  m.impl("se3_exp", &lie_unary<devo_lie_exp, LIE_K, LIE_N>);
+  m.impl("se3_log", &lie_unary<devo_lie_log, LIE_N, LIE_K>);
+  m.impl("se3_inv", &lie_unary<devo_lie_inv, LIE_N, LIE_N>);
+  m.impl("se3_mul", &lie_binary<devo_lie_mul, LIE_N, LIE_N>);
+  m.impl("se3_adj", &lie_binary<devo_lie_adj, LIE_K, LIE_K>);
+  m.impl("se3_adjT", &lie_binary<devo_lie_adjT, LIE_K, LIE_K>);
+  m.impl("se3_act", &lie_binary<devo_lie_act, 3, 3>);
+  m.impl("se3_act4", &lie_binary<devo_lie_act4, 4, 4>);
+  m.impl("se3_projector", &lie_projector);
   m.impl("loss_forward", &loss_forward);
   m.impl("loss_backward", &loss_backward);
   m.impl("frame_graph_disps", &fg_disps);
@@ -1338,24 +1353,24 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   });
   m.def("bump_version", &bump_version, "count a raw-pointer write as an in-place edit of the tensor (no launch)");
 
-  auto lie = m.def_submodule("lietorch_backends", "devo/lietorch/src/lietorch.cpp:286-316 (SE3)");
-  lie.def("expm", &lie_unary<devo_se3_exp, 7>);
-  lie.def("expm_backward", &lie_unary_bwd<devo_se3_exp_backward, 6>);
-  lie.def("logm", &lie_unary<devo_se3_log, 6>);
-  lie.def("logm_backward", &lie_unary_bwd<devo_se3_log_backward, 7>);
-  lie.def("inv", &lie_unary<devo_se3_inv, 7>);
-  lie.def("inv_backward", &lie_unary_bwd<devo_se3_inv_backward, 7>);
-  lie.def("mul", &lie_binary<devo_se3_mul, 7>);
-  lie.def("mul_backward", &lie_binary_bwd<devo_se3_mul_backward, 7>);
-  lie.def("adj", &lie_binary<devo_se3_adj, 6>);
-  lie.def("adj_backward", &lie_binary_bwd<devo_se3_adj_backward, 6>);
-  lie.def("adjT", &lie_binary<devo_se3_adjT, 6>);
-  lie.def("adjT_backward", &lie_binary_bwd<devo_se3_adjT_backward, 6>);
-  lie.def("act", &lie_binary<devo_se3_act, 3>);
-  lie.def("act_backward", &lie_binary_bwd<devo_se3_act_backward, 3>);
-  lie.def("act4", &lie_binary<devo_se3_act4, 4>);
-  lie.def("act4_backward", &lie_binary_bwd<devo_se3_act4_backward, 4>);
+  auto lie = m.def_submodule("lietorch_backends", "devo/lietorch/src/lietorch.cpp:286-316 (SO3, RxSO3, SE3, Sim3)");
+  lie.def("expm", &lie_unary<devo_lie_exp, LIE_K, LIE_N>);
+  lie.def("expm_backward", &lie_unary_bwd<devo_lie_exp_backward, LIE_N, LIE_K, LIE_K>);
+  lie.def("logm", &lie_unary<devo_lie_log, LIE_N, LIE_K>);
+  lie.def("logm_backward", &lie_unary_bwd<devo_lie_log_backward, LIE_K, LIE_N, LIE_N>);
+  lie.def("inv", &lie_unary<devo_lie_inv, LIE_N, LIE_N>);
+  lie.def("inv_backward", &lie_unary_bwd<devo_lie_inv_backward, LIE_N, LIE_N, LIE_N>);
+  lie.def("mul", &lie_binary<devo_lie_mul, LIE_N, LIE_N>);
+  lie.def("mul_backward", &lie_binary_bwd<devo_lie_mul_backward, LIE_N, LIE_N>);
+  lie.def("adj", &lie_binary<devo_lie_adj, LIE_K, LIE_K>);
+  lie.def("adj_backward", &lie_binary_bwd<devo_lie_adj_backward, LIE_K, LIE_K>);
+  lie.def("adjT", &lie_binary<devo_lie_adjT, LIE_K, LIE_K>);
+  lie.def("adjT_backward", &lie_binary_bwd<devo_lie_adjT_backward, LIE_K, LIE_K>);
+  lie.def("act", &lie_binary<devo_lie_act, 3, 3>);
+  lie.def("act_backward", &lie_binary_bwd<devo_lie_act_backward, 3, 3>);
+  lie.def("act4", &lie_binary<devo_lie_act4, 4, 4>);
+  lie.def("act4_backward", &lie_binary_bwd<devo_lie_act4_backward, 4, 4>);
   lie.def("as_matrix", &lie_as_matrix);
   lie.def("projector", &lie_projector);
-  lie.def("Jinv", &lie_binary<devo_se3_jinv, 6>);
+  lie.def("Jinv", &lie_binary<devo_lie_jinv, LIE_K, LIE_K>);
 }

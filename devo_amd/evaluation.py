@@ -72,6 +72,12 @@ class Result:
     def matched_of(self, b=0):
         return self._rows(self.matched, b)
 
+    def sim3(self):
+        """The alignments as a `lietorch.Sim3` of shape [B] (fp64, data = (t, q_xyzw, c)): `S.act(x)` is c R x + t, and it composes, inverts
+        and differentiates like any group element.  A flagged pair stays NaN."""
+        from .lietorch import Sim3
+        return Sim3(torch.cat([self.transform[:, 1:8], self.transform[:, 0:1]], -1))
+
 
 def _device(*groups):
     for g in groups:

@@ -27,7 +27,8 @@ typedef void* devo_stream_t; /* hipStream_t */
 enum { DEVO_OK = 0, DEVO_ERR_ARG = 1, DEVO_ERR_LAUNCH = 2, DEVO_ERR_UNSUPPORTED = 3, DEVO_ERR_WORKSPACE = 4 };
 enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
 
-#define DEVO_ABI_VERSION 9 /* 2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
+#define DEVO_ABI_VERSION 9 /* (devo_lie_*: SO3, RxSO3, SE3, Sim3 by group id, and devo_lie_projector joined version 9: new symbols, no argument list changed);
+                               2: fp32 split formats (devo_corr_pyramid_split, exponents), group plans (plan buffer tail); 3: per-slot conversions of a ring
                               (devo_corr_pyramid_split_frames, devo_corr_patch_transpose_range), devo_stream_capturing; 4: devo_ba_table_offsets, devo_upd_graph_tables; 5: devo_ba_forward_prepared_delta_plan, devo_ba_import_tables, devo_upd_rs_corr_f16_net32,
                               devo_upd_rs_gru_f16_out32, devo_instnorm_cl, devo_instnorm_bias_cl, devo_bias_act_cl;
                               6: devo_voxelize_windows, devo_voxel_hot_pixels, devo_voxel_rescale (and their workspace queries);
@@ -390,6 +391,38 @@ int devo_se3_act4_backward(const void* grad, const void* X, const void* p, void*
                            int dtype, devo_stream_t s);
 int devo_se3_as_matrix(const void* X, void* T44, int64_t n, int dtype, devo_stream_t s);            /* :313 as_matrix */
 int devo_se3_jinv(const void* X, const void* a, void* b, int64_t n, int dtype, devo_stream_t s);    /* :314 Jinv */
+
+/* ------------------------------------------------------------------------------------------------
+ * lietorch, all four groups (dispatch.h): group 1 SO3 (X [n,4] = q_xyzw, tangent [n,3] = phi), 2 RxSO3 (X [n,5] = q, s; tangent
+ * [n,4] = phi, sigma), 3 SE3 (as above: these calls forward to devo_se3_*), 4 Sim3 (X [n,8] = t, q, s; tangent [n,7] = tau, phi,
+ * sigma).  Same argument lists as devo_se3_* with the group id in front; gradients of group elements (N slots) hold a tangent in the
+ * first K = N - 1 slots and 0 in the last.  Points: [n,3] (act) and [n,4] (act4).  Any other group id: DEVO_ERR_ARG.
+ * devo_lie_projector: P [n,N,N] row-major, d(embedded coordinates) / d(left perturbation), last column zero (lietorch.cpp:312).
+ * ---------------------------------------------------------------------------------------------- */
+int devo_lie_exp(int group, const void* a, void* X, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_exp_backward(int group, const void* grad, const void* a, void* da, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_log(int group, const void* X, void* a, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_log_backward(int group, const void* grad, const void* X, void* dX, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_inv(int group, const void* X, void* Y, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_inv_backward(int group, const void* grad, const void* X, void* dX, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_mul(int group, const void* X, const void* Y, void* Z, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_mul_backward(int group, const void* grad, const void* X, const void* Y, void* dX, void* dY, int64_t n,
+                          int dtype, devo_stream_t s);
+int devo_lie_adj(int group, const void* X, const void* a, void* b, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_adj_backward(int group, const void* grad, const void* X, const void* a, void* dX, void* da, int64_t n,
+                          int dtype, devo_stream_t s);
+int devo_lie_adjT(int group, const void* X, const void* a, void* b, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_adjT_backward(int group, const void* grad, const void* X, const void* a, void* dX, void* da, int64_t n,
+                           int dtype, devo_stream_t s);
+int devo_lie_act(int group, const void* X, const void* p, void* q, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_act_backward(int group, const void* grad, const void* X, const void* p, void* dX, void* dp, int64_t n,
+                          int dtype, devo_stream_t s);
+int devo_lie_act4(int group, const void* X, const void* p, void* q, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_act4_backward(int group, const void* grad, const void* X, const void* p, void* dX, void* dp, int64_t n,
+                           int dtype, devo_stream_t s);
+int devo_lie_as_matrix(int group, const void* X, void* T44, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_jinv(int group, const void* X, const void* a, void* b, int64_t n, int dtype, devo_stream_t s);
+int devo_lie_projector(int group, const void* X, void* P, int64_t n, int dtype, devo_stream_t s);
 
 /* ------------------------------------------------------------------------------------------------
  * Update operator pieces (devo/enet.py:32-99, devo/blocks.py:15-48) — the reductions and
