@@ -2000,3 +2000,98 @@ int devo_ba_edge_terms_backward(const float* g_terms, const float* gate, int E, 
 }
 
 }  // extern "C"
+
+namespace devo {
+
+#define LOOP(i, n) for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)blockDim.x * gridDim.x)
+
+template <typename T> DEVO_HD void store_grad7(T* p, const T* g6) {
+#pragma unroll
+  for (int k = 0; k < 6; k++) p[k] = g6[k];
+  p[6] = T(0);
+}
+
+// The update step of the differentiable BA (devo/ba.py:172-182) as one kernel per direction: poses[fixedp .. fixedp + n_opt) <- Exp(dX_i) * pose_i
+// (`poses.retr`), every patch's inverse depth <- clamp(d + dZ_k, dmin, dmax) over its P x P pixels, everything else copied.  The reference
+// (and round 3) ran it as torch.stack / clamp / zeros / slice assignment + the Exp and Mul group ops: ~8 launches forward, ~12 backward.
+// Work item i < N: pose i; item N + k: patch k.
+__global__ void k_ba_apply_step(const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ dX, const float* __restrict__ dZ,
+                                int N, int Np, int PP, int fixedp, int n_opt, float dmin, float dmax, float* __restrict__ poses_out, float* __restrict__ patches_out) {
+  LOOP(i, (int64_t)N + Np) {
+    if (i < N) {
+      SE3<float> X = SE3<float>::load(poses + i * 7);
+      if (i >= fixedp && i < fixedp + n_opt) X = se3_exp<float>(dX + (i - fixedp) * 6).mul(X);
+      X.store(poses_out + i * 7);
+    } else {
+      const int64_t k = i - N;
+      const float* p = patches + k * 3 * PP;
+      float* o = patches_out + k * 3 * PP;
+      const float dz = dZ[k];
+      for (int j = 0; j < 2 * PP; j++) o[j] = p[j];
+      for (int j = 2 * PP; j < 3 * PP; j++) o[j] = fminf(fmaxf(p[j] + dz, dmin), dmax);
+    }
+  }
+}
+// adjoint: g_poses_out [N,7] (lietorch's embedding: tangent in the first six), g_patches_out -> g_poses, g_patches, g_dX [6 n_opt], g_dZ [Np]
+__global__ void k_ba_apply_step_bwd(const float* __restrict__ poses, const float* __restrict__ patches, const float* __restrict__ dX, const float* __restrict__ dZ,
+                                    const float* __restrict__ g_poses_out, const float* __restrict__ g_patches_out, int N, int Np, int PP, int fixedp,
+                                    int n_opt, float dmin, float dmax, float* __restrict__ g_poses, float* __restrict__ g_patches, float* __restrict__ g_dX,
+                                    float* __restrict__ g_dZ) {
+  LOOP(i, (int64_t)N + Np) {
+    if (i < N) {
+      if (i >= fixedp && i < fixedp + n_opt) {
+        const float* a = dX + (i - fixedp) * 6;
+        float g[7], o[6], ga7[7];
+#pragma unroll
+        for (int k = 0; k < 7; k++) g[k] = g_poses_out ? g_poses_out[i * 7 + k] : 0.0f;
+        se3_exp<float>(a).row_times_Adj(g, o);                          // Mul's adjoint (lietorch_gpu.cu:112-125): d left = g, d right = g Adj(left)
+        store_grad7(g_poses + i * 7, o);
+        store_grad7(ga7, g);
+        row_times_left_jacobian<float>(ga7, a, g_dX + (i - fixedp) * 6); // Exp's adjoint (:32-44)
+      } else {
+#pragma unroll
+        for (int k = 0; k < 7; k++) g_poses[i * 7 + k] = g_poses_out ? g_poses_out[i * 7 + k] : 0.0f;
+      }
+    } else {
+      const int64_t k = i - N;
+      const float* p = patches + k * 3 * PP;
+      const float* g = g_patches_out ? g_patches_out + k * 3 * PP : nullptr;
+      float* o = g_patches + k * 3 * PP;
+      const float dz = dZ[k];
+      float s = 0.0f;
+      for (int j = 0; j < 2 * PP; j++) o[j] = g ? g[j] : 0.0f;
+      for (int j = 2 * PP; j < 3 * PP; j++) {
+        const float d = p[j] + dz;
+        const float gj = (g && d >= dmin && d <= dmax) ? g[j] : 0.0f;    // clamp passes the gradient inside [dmin, dmax] (ATen's clamp_backward mask)
+        o[j] = gj; s += gj;
+      }
+      g_dZ[k] = s;
+    }
+  }
+}
+
+}  // namespace devo
+
+extern "C" {
+
+int devo_ba_apply_step(const float* poses, const float* patches, const float* dX, const float* dZ, int N, int Np, int P, int fixedp, int n_opt,
+                       float dmin, float dmax, float* poses_out, float* patches_out, devo_stream_t s) {
+  if (N < 0 || Np < 0 || P <= 0 || fixedp < 0 || n_opt < 0 || fixedp + n_opt > N) { set_error("devo_ba_apply_step: bad sizes"); return DEVO_ERR_ARG; }
+  if (N + Np == 0) return DEVO_OK;
+  if (!poses || !patches || !dZ || !poses_out || !patches_out || (n_opt > 0 && !dX)) { set_error("devo_ba_apply_step: null tensor"); return DEVO_ERR_ARG; }
+  hipLaunchKernelGGL(k_ba_apply_step, dim3((unsigned)((N + Np + 255) / 256)), dim3(256), 0, (hipStream_t)s, poses, patches, dX, dZ, N, Np, P * P, fixedp, n_opt,
+                     dmin, dmax, poses_out, patches_out);
+  return check_launch("devo_ba_apply_step");
+}
+int devo_ba_apply_step_backward(const float* poses, const float* patches, const float* dX, const float* dZ, const float* g_poses_out, const float* g_patches_out,
+                                int N, int Np, int P, int fixedp, int n_opt, float dmin, float dmax, float* g_poses, float* g_patches, float* g_dX,
+                                float* g_dZ, devo_stream_t s) {
+  if (N < 0 || Np < 0 || P <= 0 || fixedp < 0 || n_opt < 0 || fixedp + n_opt > N) { set_error("devo_ba_apply_step_backward: bad sizes"); return DEVO_ERR_ARG; }
+  if (N + Np == 0) return DEVO_OK;
+  if (!poses || !patches || !dZ || !g_poses || !g_patches || !g_dZ || (n_opt > 0 && (!dX || !g_dX))) { set_error("devo_ba_apply_step_backward: null tensor"); return DEVO_ERR_ARG; }
+  hipLaunchKernelGGL(k_ba_apply_step_bwd, dim3((unsigned)((N + Np + 255) / 256)), dim3(256), 0, (hipStream_t)s, poses, patches, dX, dZ, g_poses_out, g_patches_out,
+                     N, Np, P * P, fixedp, n_opt, dmin, dmax, g_poses, g_patches, g_dX, g_dZ);
+  return check_launch("devo_ba_apply_step_backward");
+}
+
+}  // extern "C"

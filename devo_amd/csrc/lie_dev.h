@@ -9,7 +9,8 @@
 //   Sim3   4   t, q_xyzw, s      (8)  tau, phi, sigma  (7)
 //
 // One generic implementation: an element is (t, q, s) with t = 0 / s = 1 where the group has none, a tangent (tau, phi, sigma) with
-// tau = 0 / sigma = 0 likewise, and every formula below is Sim3's, which restricts to the three others.
+// tau = 0 / sigma = 0 likewise, and every formula below is Sim3's, which restricts to the three others.  SE3 is the exception where that
+// restriction would not be se3_dev.h's arithmetic: see "SE3" below.
 #pragma once
 #include "se3_dev.h"
 
@@ -79,6 +80,22 @@ template <int G, typename T> DEVO_HD void elem_store(const Elem<T>& X, T* p) {
   if (LieG<G>::HAS_S) p[o + 4] = X.s;
 }
 
+// ---- SE3 --------------------------------------------------------------------------------------
+// SE3 keeps the arithmetic of se3_dev.h, which ba.hip, loss.hip, frames.hip, graph.hip and transform.hip compute with.  With s = 1 and no
+// sigma most generic formulas are se3_dev.h's to the bit (load / store, inv, mul, act, the 4x4 matrix: x * 1 and x + 0 * t fold away).
+// Not so where se3_dev.h rotates with the matrix qmat(q) (Adj, Adj^T, the point gradient), where x + 0 * y would have to equal x
+// (row_times_ad: it does not for a non-finite y), and in exp / log and the Jacobians, whose Q block se3_dev.h has in closed form (se3_calcQ)
+// where Sim3 sums a series.  elem_adj, elem_adjT, row_times_sR, lie_exp and lie_log start with an `if constexpr (G == 3)` that calls se3_dev.h
+// through these converters.  row_times_ad and the three Jacobian products refuse G = 3 (SE3_IN_KERNEL): the kernels that need them (adj_bwd,
+// adjT_bwd, exp_bwd, log_bwd, jinv in lie.hip) call se3_dev.h on the operands in memory, in the order the SE3-only kernels had.  Through the
+// converters the compiler pairs multiplies and adds into fmas differently (the choice follows the order of the loads), which moves last bits.
+#define SE3_IN_KERNEL(G) static_assert(G != 3, "SE3: lie.hip's kernel calls se3_dev.h directly (see \"SE3\" in lie_dev.h)")
+template <typename T> struct Tan6 { T v[6]; };
+template <typename T> DEVO_HD Tan6<T> tan6(const Tan<T>& a) { Tan6<T> r; tan_store<3, T>(a, r.v); return r; }
+template <typename T> DEVO_HD Tan<T> tan_of(const Tan6<T>& r) { return tan_load<3, T>(r.v); }
+template <typename T> DEVO_HD SE3<T> se3_of(const Elem<T>& X) { SE3<T> Y; Y.t = X.t; Y.q = X.q; return Y; }
+template <typename T> DEVO_HD Elem<T> elem_of(const SE3<T>& X) { return Elem<T>{X.t, X.q, T(1)}; }
+
 // ---- group structure --------------------------------------------------------------------------
 template <typename T> DEVO_HD Elem<T> elem_inv(const Elem<T>& X) {                      // so3.h:43, rxso3.h:46-48, sim3.h:43-45
   Elem<T> Y;
@@ -96,14 +113,16 @@ template <typename T> DEVO_HD Elem<T> elem_mul(const Elem<T>& X, const Elem<T>& 
 }
 template <typename T> DEVO_HD V3<T> elem_act(const Elem<T>& X, V3<T> p) { return X.s * qrot(X.q, p) + X.t; }      // rxso3.h:59-63, sim3.h:56-58
 // Adj = [[sR, [t]x R, -t], [0, R, 0], [0, 0, 1]]   (sim3.h:89-101; rxso3.h:70-74 and so3.h:67 are its lower-right blocks)
-template <typename T> DEVO_HD Tan<T> elem_adj(const Elem<T>& X, const Tan<T>& a) {
+template <int G, typename T> DEVO_HD Tan<T> elem_adj(const Elem<T>& X, const Tan<T>& a) {
+  if constexpr (G == 3) { Tan6<T> b; se3_of(X).adj(tan6(a).v, b.v); return tan_of(b); }
   Tan<T> b;
   b.phi = qrot(X.q, a.phi);
   b.tau = X.s * qrot(X.q, a.tau) + cross(X.t, b.phi) - a.sigma * X.t;
   b.sigma = a.sigma;
   return b;
 }
-template <typename T> DEVO_HD Tan<T> elem_adjT(const Elem<T>& X, const Tan<T>& a) {    // Adj^T a == (a^T Adj)^T
+template <int G, typename T> DEVO_HD Tan<T> elem_adjT(const Elem<T>& X, const Tan<T>& a) {   // Adj^T a == (a^T Adj)^T
+  if constexpr (G == 3) { Tan6<T> b; se3_of(X).adjT(tan6(a).v, b.v); return tan_of(b); }
   const Q4<T> qi = qconj(X.q);
   Tan<T> b;
   b.tau = X.s * qrot(qi, a.tau);
@@ -112,12 +131,18 @@ template <typename T> DEVO_HD Tan<T> elem_adjT(const Elem<T>& X, const Tan<T>& a
   return b;
 }
 // a(1xK) * ad(b),  ad(b) = [[Phi + sigma I, Tau, -tau], [0, Phi, 0], [0, 0, 0]]  (sim3.h:126-142);  row * hat(v) = row x v
-template <typename T> DEVO_HD Tan<T> row_times_ad(const Tan<T>& a, const Tan<T>& b) {
+template <int G, typename T> DEVO_HD Tan<T> row_times_ad(const Tan<T>& a, const Tan<T>& b) {
+  SE3_IN_KERNEL(G);
   Tan<T> o;
   o.tau = cross(a.tau, b.phi) + b.sigma * a.tau;
   o.phi = cross(a.tau, b.tau) + cross(a.phi, b.phi);
   o.sigma = -dot(a.tau, b.tau);
   return o;
+}
+// g(1x3) * (sR): the point gradient of act / act4
+template <int G, typename T> DEVO_HD V3<T> row_times_sR(V3<T> g, const Elem<T>& X) {
+  if constexpr (G == 3) return mulTv(qmat(X.q), g);
+  return X.s * qrot(qconj(X.q), g);
 }
 template <typename T> DEVO_HD Tan<T> tan_neg(const Tan<T>& a) { return Tan<T>{-a.tau, -a.phi, -a.sigma}; }
 
@@ -188,6 +213,7 @@ template <typename T> DEVO_HD WCoef<T> so3_jl_inv_coef(T theta2, T theta) { retu
 
 // ---- exp / log --------------------------------------------------------------------------------
 template <int G, typename T> DEVO_HD Elem<T> lie_exp(const Tan<T>& a) {                 // so3.h:153-168, rxso3.h:168-188, se3.h:134-142, sim3.h:156-165
+  if constexpr (G == 3) return elem_of(se3_exp<T>(tan6(a).v));
   Elem<T> X;
   X.q = so3_exp(a.phi);
   X.s = LieG<G>::HAS_S ? t_exp<T>(a.sigma) : T(1);
@@ -199,6 +225,7 @@ template <int G, typename T> DEVO_HD Elem<T> lie_exp(const Tan<T>& a) {         
   return X;
 }
 template <int G, typename T> DEVO_HD Tan<T> lie_log(const Elem<T>& X) {                 // so3.h:115-151, rxso3.h:131-166, se3.h:124-132, sim3.h:145-154
+  if constexpr (G == 3) { Tan6<T> a; se3_log<T>(se3_of(X), a.v); return tan_of(a); }
   Tan<T> a;
   a.phi = so3_log(X.q);
   a.sigma = LieG<G>::HAS_S ? t_log<T>(X.s) : T(0);
@@ -249,6 +276,7 @@ template <typename T> DEVO_HD V3<T> rows_times(const V3<T>* Q, V3<T> v) { return
 
 // g(1xK) * J_l(a): the adjoint of Exp (lietorch_gpu.cu:32-44)
 template <int G, typename T> DEVO_HD Tan<T> row_times_jl(const Tan<T>& g, const Tan<T>& a) {
+  SE3_IN_KERNEL(G);
   const T theta2 = dot(a.phi, a.phi), theta = t_sqrt<T>(theta2);
   Tan<T> o;
   o.phi = abc_applyT(so3_jl_coef<T>(theta2, theta), a.phi, g.phi);
@@ -264,6 +292,7 @@ template <int G, typename T> DEVO_HD Tan<T> row_times_jl(const Tan<T>& g, const 
 }
 // g(1xK) * J_l(a)^-1 by block back-substitution: the adjoint of Log (lietorch_gpu.cu:58-70)
 template <int G, typename T> DEVO_HD Tan<T> row_times_jl_inv(const Tan<T>& g, const Tan<T>& a) {
+  SE3_IN_KERNEL(G);
   const T theta2 = dot(a.phi, a.phi), theta = t_sqrt<T>(theta2);
   const WCoef<T> ji = so3_jl_inv_coef<T>(theta2, theta);
   Tan<T> o;
@@ -281,6 +310,7 @@ template <int G, typename T> DEVO_HD Tan<T> row_times_jl_inv(const Tan<T>& g, co
 }
 // J_l(a)^-1 v: the forward op Jinv (lietorch_gpu.cu:283-294), the same inverse
 template <int G, typename T> DEVO_HD Tan<T> jl_inv_times(const Tan<T>& a, const Tan<T>& v) {
+  SE3_IN_KERNEL(G);
   const T theta2 = dot(a.phi, a.phi), theta = t_sqrt<T>(theta2);
   Tan<T> o;
   o.phi = abc_apply(so3_jl_inv_coef<T>(theta2, theta), a.phi, v.phi);

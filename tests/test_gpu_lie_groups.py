@@ -1,4 +1,4 @@
-"""SO3, RxSO3, SE3 and Sim3 on the GPU (csrc/lie_groups.hip, csrc/lie.hip) through the module interface `lietorch_backends` and the classes of
+"""SO3, RxSO3, SE3 and Sim3 on the GPU (csrc/lie.hip, csrc/lie_dev.h) through the module interface `lietorch_backends` and the classes of
 devo_amd.lietorch, against the branch-free fp64 reference tests/lie_groups_ref.py (checked on the CPU by tests/test_lie_groups_ref_cpu.py).
 Tolerances are those of tests/test_gpu_lietorch.py: 1e-11 (fp64) and 2e-5 (fp32) relative to max(1, |reference|)."""
 import math
