@@ -9,6 +9,7 @@
 //   corr_fwd_mfma_kernel (corr_mfma.h, fp32 / C = 128): position-centric, lanes = box pixels, products on the matrix cores;
 //   corr_fwd_cl_kernel (below, fp32 / fp16, any C % 8 == 0): tap-centric, box staged through LDS, DPP-broadcast FMAs.
 #include "common.h"
+#include "f16split.h"
 #include "corr_tile.h"
 #include "corr_plan.h"
 #include <hip/hip_fp16.h>

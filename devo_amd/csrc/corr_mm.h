@@ -42,18 +42,12 @@ constexpr int MM_CAP = 160;            // result area of a box, radius <= 3 (pos
 // magnitude lands in [2^13, 2^14)) is the fp16 pair  hi = rn(x 2^-e),  lo = rn(x 2^-e - hi):  x 2^-e = hi + lo to 2^-22 relative (a lo below
 // fp16's normal range keeps 2^-25 absolute, i.e. 2^-39 of the group's largest magnitude).  The power-of-two scaling is exact, no input
 // magnitude overflows fp16, and the kernel multiplies the blended sums by 2^(e_patch + e_frame) at the end (folded into the blend weights).
-// (v_cvt_pk_f16_f32: two values per instruction; v_fma_mix: fp32 arithmetic on the fp16 hi.)
-__device__ __forceinline__ void mm_split2(float a, float b, unsigned& h, unsigned& l) {
-  asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h) : "v"(a), "v"(b));
-  // (mixlo keeps the destination's upper half, which mixhi then overwrites: no initialisation needed)
-  asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l) : "v"(h), "v"(a));
-  asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l) : "v"(h), "v"(b));
-}
+// The pair split itself is split2 (f16split.h, which corr.hip includes at file scope).
 // 8 fp32 values, scaled by 2^-e -> the 32-byte split record (hi0..7 | lo0..7)
 __device__ __forceinline__ void mm_split8_scaled(const float* x, int e, v4u32& hi, v4u32& lo) {
   unsigned h[4], l[4];
 #pragma unroll
-  for (int j = 0; j < 4; j++) mm_split2(ldexpf(x[2 * j], -e), ldexpf(x[2 * j + 1], -e), h[j], l[j]);
+  for (int j = 0; j < 4; j++) split2(ldexpf(x[2 * j], -e), ldexpf(x[2 * j + 1], -e), h[j], l[j]);
   hi = v4u32{h[0], h[1], h[2], h[3]};
   lo = v4u32{l[0], l[1], l[2], l[3]};
 }
@@ -268,8 +262,7 @@ __global__ __launch_bounds__(64 * (NW > 1 ? NW : MM_EPW)) __attribute__((amdgpu_
         const int gy = ry0 + (int)row, gx = rx0 + (int)col;
         const bool ok = blk < (unsigned)(C / 8) && (unsigned)gy < (unsigned)lv1.H2 && (unsigned)gx < (unsigned)lv1.W2;
         const unsigned voff = ok ? blk * bb + (unsigned)gy * shb1 + (unsigned)gx * swb1 + (cbyte - col * RPOS) : 0x80000000u;
-        const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((int)(lds0 + (unsigned)q * 1024u));
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "s"(dst) : "memory");
+        lds_dma16(voff, rs, lds0 + (unsigned)q * 1024u);
       }
       region_pending = true;
     }

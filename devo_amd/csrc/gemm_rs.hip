@@ -15,17 +15,14 @@
 //   * the chain form (Linear - ReLU - Linear, mlp2.hip's job) writes relu(h) back into the row tile and runs the second layer from there.
 // Traffic into a CU per 128 rows: 96 KB of rows + 288 KB of weights (linear.hip: 4 x (96 + 72) KB through LDS-DMA).
 #include "common.h"
+#include "f16split.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 
 namespace devo {
 
-typedef _Float16 rs_h8 __attribute__((ext_vector_type(8)));
-typedef float rs_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned rs_u4 __attribute__((ext_vector_type(4)));
-typedef _Float16 rs_h4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ rs_f4 rs_cvt4(rs_h4 h) { return __builtin_convertvector(h, rs_f4); }
-__device__ __forceinline__ rs_h4 rs_pack4(rs_f4 v) { return __builtin_convertvector(v, rs_h4); }
+__device__ __forceinline__ f4 rs_cvt4(h4 h) { return __builtin_convertvector(h, f4); }
+__device__ __forceinline__ h4 rs_pack4(f4 v) { return __builtin_convertvector(v, h4); }
 
 constexpr int RS_NW = 8;                           // waves per workgroup
 constexpr int RS_NT = 3;                           // column tiles of 16 per wave
@@ -35,7 +32,7 @@ constexpr int RS_EPI_LD = RS_NT * 16 + 4;          // row pitch (floats) of a wa
 
 // W fp16 (element (n, k) at W[n * s_n + k * s_k]; N a multiple of 384) -> [N / 384][8 waves][ceil(K / 32)][3 tiles][64 lanes][16 B]:
 // lane (n, kg) of tile t holds k = 32 s + 8 kg .. + 7 of column 384 nb + 48 w + 16 t + n (zeros past K)
-__global__ __launch_bounds__(256) void k_rs_pack_f16(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, rs_u4* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_rs_pack_f16(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, u4* __restrict__ out) {
   const int nk = (K + 31) / 32;
   const long long total = (long long)(N / RS_BN) * RS_NW * nk * RS_NT * 64;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -45,10 +42,7 @@ __global__ __launch_bounds__(256) void k_rs_pack_f16(const __half* __restrict__ 
     const int s = (int)(r % nk); r /= nk;
     const int w = (int)(r % RS_NW), nb = (int)(r / RS_NW);
     const int n = nb * RS_BN + 48 * w + 16 * t + (lane & 15), k0 = 32 * s + 8 * (lane >> 4);
-    rs_h8 v;
-#pragma unroll
-    for (int e = 0; e < 8; e++) v[e] = k0 + e < K ? (_Float16)__half2float(W[(int64_t)n * s_n + (int64_t)(k0 + e) * s_k]) : (_Float16)0.f;
-    out[i] = __builtin_bit_cast(rs_u4, v);
+    out[i] = gather8_f16(reinterpret_cast<const _Float16*>(W), s_n, s_k, n, k0, K);
   }
 }
 
@@ -59,7 +53,7 @@ __device__ __forceinline__ unsigned rs_whole_dwords(int64_t bytes) { return (uns
 
 // y[M, N] = act(x[M, K] W^T + bias) [+ residual], N = 384 NB.  grid = ceil(M / (16 MT)).  NK = K steps of 32 (K <= 32 NK).
 template <int MT, int NK>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4 : 1, MT <= 3 ? 4 : 8))) void k_rs_linear_f16(const __half* __restrict__ x, int64_t ldx, const rs_u4* __restrict__ wimg,
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4 : 1, MT <= 3 ? 4 : 8))) void k_rs_linear_f16(const __half* __restrict__ x, int64_t ldx, const u4* __restrict__ wimg,
                                                         const __half* __restrict__ bias, const __half* residual, __half* y, int64_t ldy, int M,
                                                         int NB, int K, int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char rs_lds[];
@@ -69,9 +63,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(x), 0, rs_whole_dwords(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(wimg), 0, (unsigned)((int64_t)NB * RS_NW * NK * RS_NT * 1024), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(wimg), 0, (unsigned)((int64_t)NB * RS_NW * NK * RS_NT * 1024), 0x00020000);
   // ---- the rows: memory -> registers -> LDS (piece p = 16 bytes: row p / PPR, halves 8 (p % PPR) .. + 7)
-  rs_u4 ap[AP];
+  u4 ap[AP];
 #pragma unroll
   for (int i = 0; i < AP; i++) {
     const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
@@ -79,7 +73,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
     ap[i] = __builtin_amdgcn_raw_buffer_load_b128(rsx, ok ? (unsigned)(((int64_t)(row0 + row) * ldx) * 2 + 16 * c) : OFF_NONE, 0, 0);
   }
   // ---- this wave's weights: K step s, tile t = 1 KB at ((nb * 8 + w) * NK + s) * 3 + t
-  rs_u4 b[RS_RB][RS_NT];
+  u4 b[RS_RB][RS_NT];
   const unsigned bvoff = (unsigned)lane * 16u;
   auto load_b = [&](int nb, int s, int slot) {
 #pragma unroll
@@ -92,30 +86,30 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
   for (int i = 0; i < AP; i++) {
     const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
     if (8 * c + 8 > K && 8 * c < K) {                                  // a K that is not a multiple of 8: what lies behind the row is not part of it
-      rs_h8 v = __builtin_bit_cast(rs_h8, ap[i]);
+      h8 v = __builtin_bit_cast(h8, ap[i]);
 #pragma unroll
       for (int e = 0; e < 8; e++) v[e] = 8 * c + e < K ? v[e] : (_Float16)0.f;
-      ap[i] = __builtin_bit_cast(rs_u4, v);
+      ap[i] = __builtin_bit_cast(u4, v);
     }
-    if (p < NPIECE) *reinterpret_cast<rs_u4*>(rs_lds + row * PITCH + 16 * c) = ap[i];
+    if (p < NPIECE) *reinterpret_cast<u4*>(rs_lds + row * PITCH + 16 * c) = ap[i];
   }
   __syncthreads();
   const unsigned char* arow = rs_lds + mi * PITCH + 16 * kg;          // this lane's piece of row 16 mt + mi, K step s: + 16 mt PITCH + 64 s
   float* tile = reinterpret_cast<float*>(rs_lds) + wv * (16 * RS_EPI_LD);
   for (int nb = 0; nb < NB; nb++) {
-    rs_f4 acc[MT][RS_NT];
+    f4 acc[MT][RS_NT];
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
-    rs_u4 af[2][MT];
+      for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
+    u4 af[2][MT];
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) af[0][mt] = *reinterpret_cast<const rs_u4*>(arow + 16 * mt * PITCH);
+    for (int mt = 0; mt < MT; mt++) af[0][mt] = *reinterpret_cast<const u4*>(arow + 16 * mt * PITCH);
 #pragma unroll
     for (int s = 0; s < NK; s++) {
       if (s + 1 < NK) {
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) af[(s + 1) & 1][mt] = *reinterpret_cast<const rs_u4*>(arow + 16 * mt * PITCH + 64 * (s + 1));
+        for (int mt = 0; mt < MT; mt++) af[(s + 1) & 1][mt] = *reinterpret_cast<const u4*>(arow + 16 * mt * PITCH + 64 * (s + 1));
       }
       if (s + RS_RB - 1 < NK) load_b(nb, s + RS_RB - 1, (s + RS_RB - 1) % RS_RB);
       __builtin_amdgcn_sched_barrier(0);
@@ -123,7 +117,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
       for (int mt = 0; mt < MT; mt++)
 #pragma unroll
         for (int t = 0; t < RS_NT; t++)
-          acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, b[s % RS_RB][t]), __builtin_bit_cast(rs_h8, af[s & 1][mt]), acc[mt][t], 0, 0, 0);
+          acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, b[s % RS_RB][t]), __builtin_bit_cast(h8, af[s & 1][mt]), acc[mt][t], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
     // the next pass's first weights travel while this one's results leave
@@ -137,37 +131,35 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
     if (last) __syncthreads();
     float* tl = last ? tile : reinterpret_cast<float*>(rs_lds + ROWS * PITCH) + wv * (16 * RS_EPI_LD);
     const int col_w = nb * RS_BN + 48 * wv;
-    rs_f4 bs[RS_NT];
+    f4 bs[RS_NT];
 #pragma unroll
-    for (int t = 0; t < RS_NT; t++) bs[t] = bias ? rs_cvt4(*reinterpret_cast<const rs_h4*>(reinterpret_cast<const _Float16*>(bias) + col_w + 16 * t + 4 * kg)) : rs_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RS_NT; t++) bs[t] = bias ? rs_cvt4(*reinterpret_cast<const h4*>(reinterpret_cast<const _Float16*>(bias) + col_w + 16 * t + 4 * kg)) : f4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) {
-        rs_f4 v = acc[mt][t] + bs[t];
+        f4 v = acc[mt][t] + bs[t];
 #pragma unroll
         for (int r = 0; r < 4; r++) v[r] = col_w + 16 * t + 4 * kg + r >= relu_from ? fmaxf(v[r], 0.f) : v[r];
-        *reinterpret_cast<rs_f4*>(tl + mi * RS_EPI_LD + 16 * t + 4 * kg) = v;
+        *reinterpret_cast<f4*>(tl + mi * RS_EPI_LD + 16 * t + 4 * kg) = v;
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_handoff();
 #pragma unroll
       for (int it = 0; it < 2; it++) {                                 // 16 rows x 6 pieces of 8 columns
         const int idx = it * 64 + lane, r = idx / 6, c = idx - r * 6;
         const int row = row0 + 16 * mt + r;
         if (idx < 96 && row < M) {
-          rs_f4 v0 = *reinterpret_cast<const rs_f4*>(tl + r * RS_EPI_LD + 8 * c), v1 = *reinterpret_cast<const rs_f4*>(tl + r * RS_EPI_LD + 8 * c + 4);
+          f4 v0 = *reinterpret_cast<const f4*>(tl + r * RS_EPI_LD + 8 * c), v1 = *reinterpret_cast<const f4*>(tl + r * RS_EPI_LD + 8 * c + 4);
           __half* dst = y + (int64_t)row * ldy + col_w + 8 * c;
           if (residual) {                                              // (may be y itself: read, then written, by this lane)
-            const rs_h8 q = __builtin_bit_cast(rs_h8, *reinterpret_cast<const rs_u4*>(residual + (int64_t)row * ldy + col_w + 8 * c));
+            const h8 q = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(residual + (int64_t)row * ldy + col_w + 8 * c));
             v0.x += (float)q[0]; v0.y += (float)q[1]; v0.z += (float)q[2]; v0.w += (float)q[3];
             v1.x += (float)q[4]; v1.y += (float)q[5]; v1.z += (float)q[6]; v1.w += (float)q[7];
           }
-          rs_h8 o;
+          h8 o;
           o[0] = (_Float16)v0.x; o[1] = (_Float16)v0.y; o[2] = (_Float16)v0.z; o[3] = (_Float16)v0.w;
           o[4] = (_Float16)v1.x; o[5] = (_Float16)v1.y; o[6] = (_Float16)v1.z; o[7] = (_Float16)v1.w;
-          *reinterpret_cast<rs_u4*>(dst) = __builtin_bit_cast(rs_u4, o);
+          *reinterpret_cast<u4*>(dst) = __builtin_bit_cast(u4, o);
         }
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -184,7 +176,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(MT <= 3 ? 4
 // LayerNorm statistics of a row are summed across the eight waves through LDS.  Rounding points are those of the layer-by-layer path
 // (every layer output and LayerNorm output rounded to fp16).
 template <int NK>
-__device__ __forceinline__ void rs_prefetch(const __amdgpu_buffer_rsrc_t rsw, unsigned wbase, unsigned bvoff, rs_u4 (&b)[RS_RB][RS_NT]) {
+__device__ __forceinline__ void rs_prefetch(const __amdgpu_buffer_rsrc_t rsw, unsigned wbase, unsigned bvoff, u4 (&b)[RS_RB][RS_NT]) {
 #pragma unroll
   for (int s = 0; s < RS_RB - 1 && s < NK; s++)
 #pragma unroll
@@ -194,17 +186,17 @@ __device__ __forceinline__ void rs_prefetch(const __amdgpu_buffer_rsrc_t rsw, un
 // acc += rows (LDS tile, this lane's pieces at arow + 16 mt PITCH + 64 s) x this wave's weight stream (steps 0 .. RS_RB - 2 already in b).
 // NEXT: the loop's last steps request the first RS_RB - 1 steps of the stream the NEXT loop multiplies (no bubble between products).
 template <int MT, int NK, int PITCH, bool NEXT = false>
-__device__ __forceinline__ void rs_kloop(const unsigned char* arow, const __amdgpu_buffer_rsrc_t rsw, unsigned wbase, unsigned bvoff, rs_u4 (&b)[RS_RB][RS_NT],
-                                         rs_f4 (&acc)[MT][RS_NT], const __amdgpu_buffer_rsrc_t nrsw = __amdgpu_buffer_rsrc_t(), unsigned nwbase = 0) {
+__device__ __forceinline__ void rs_kloop(const unsigned char* arow, const __amdgpu_buffer_rsrc_t rsw, unsigned wbase, unsigned bvoff, u4 (&b)[RS_RB][RS_NT],
+                                         f4 (&acc)[MT][RS_NT], const __amdgpu_buffer_rsrc_t nrsw = __amdgpu_buffer_rsrc_t(), unsigned nwbase = 0) {
   static_assert(NK % RS_RB == 0, "ring slots line up across loops");
-  rs_u4 af[2][MT];
+  u4 af[2][MT];
 #pragma unroll
-  for (int mt = 0; mt < MT; mt++) af[0][mt] = *reinterpret_cast<const rs_u4*>(arow + 16 * mt * PITCH);
+  for (int mt = 0; mt < MT; mt++) af[0][mt] = *reinterpret_cast<const u4*>(arow + 16 * mt * PITCH);
 #pragma unroll
   for (int s = 0; s < NK; s++) {
     if (s + 1 < NK) {
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) af[(s + 1) & 1][mt] = *reinterpret_cast<const rs_u4*>(arow + 16 * mt * PITCH + 64 * (s + 1));
+      for (int mt = 0; mt < MT; mt++) af[(s + 1) & 1][mt] = *reinterpret_cast<const u4*>(arow + 16 * mt * PITCH + 64 * (s + 1));
     }
     if (s + RS_RB - 1 < NK) {
 #pragma unroll
@@ -220,17 +212,9 @@ __device__ __forceinline__ void rs_kloop(const unsigned char* arow, const __amdg
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
       for (int t = 0; t < RS_NT; t++)
-        acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, b[s % RS_RB][t]), __builtin_bit_cast(rs_h8, af[s & 1][mt]), acc[mt][t], 0, 0, 0);
+        acc[mt][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, b[s % RS_RB][t]), __builtin_bit_cast(h8, af[s & 1][mt]), acc[mt][t], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
-}
-
-__device__ __forceinline__ float rs_row16_sum(float v) {               // over the 16 lanes of a DPP row, result in all of them
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));
-  return v;
 }
 
 // LayerNorm statistics of a workgroup's 16 MT rows while their elements are accumulators (this lane: 12 columns of row 16 mt + mi): sums over
@@ -239,7 +223,7 @@ __device__ __forceinline__ float rs_row16_sum(float v) {               // over t
 // its spread 1e-2 of its rstd to the cancellation (measured: tests/test_gpu_update_chains.py, the `offset` set).  Ends behind a barrier.
 // (Every lane adding the eight partials of its own rows — two barriers less — was measured too: 3 % of the operator slower, not faster.)
 template <int MT>
-__device__ __forceinline__ void rs_row_stats(const rs_f4 (&acc)[MT][RS_NT], float* part, float* stat, float eps, int tid, int wv, int mi, int kg) {
+__device__ __forceinline__ void rs_row_stats(const f4 (&acc)[MT][RS_NT], float* part, float* stat, float eps, int tid, int wv, int mi, int kg) {
   constexpr int ROWS = 16 * MT, D = 384;
 #pragma unroll
   for (int pass = 0; pass < 2; pass++) {
@@ -269,8 +253,8 @@ __device__ __forceinline__ void rs_row_stats(const rs_f4 (&acc)[MT][RS_NT], floa
 struct RsGru {
   const __half* x; const __half* hy; const int* grp;                   // rows: x[e] + hy[grp[e]]
   const __half* ln0_g; const __half* ln0_b;
-  const rs_u4* w_gr[2]; const __half* b_gr[2];                         // [gate | res[0]] images (N = 768) and biases of the two GatedResiduals
-  const rs_u4* w_r2[2]; const __half* b_r2[2];                         // res[2]
+  const u4* w_gr[2]; const __half* b_gr[2];                         // [gate | res[0]] images (N = 768) and biases of the two GatedResiduals
+  const u4* w_r2[2]; const __half* b_r2[2];                         // res[2]
   const __half* ln2_g; const __half* ln2_b;
   const __half* Wd; const __half* bd; const __half* Ww; const __half* bw;
   __half* net_out; __half* delta; __half* weight;
@@ -298,11 +282,11 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
   __amdgpu_buffer_rsrc_t rs_gr[2], rs_r2[2];
 #pragma unroll
   for (int i = 0; i < 2; i++) {
-    rs_gr[i] = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w_gr[i]), 0, 2u * D * D * 2u, 0x00020000);
-    rs_r2[i] = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w_r2[i]), 0, (unsigned)(D * D * 2), 0x00020000);
+    rs_gr[i] = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(a.w_gr[i]), 0, 2u * D * D * 2u, 0x00020000);
+    rs_r2[i] = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(a.w_r2[i]), 0, (unsigned)(D * D * 2), 0x00020000);
   }
   auto wbase = [&](int nb) { return (unsigned)(((nb * RS_NW + wv) * NK) * RS_NT * 1024); };
-  rs_u4 b[RS_RB][RS_NT];
+  u4 b[RS_RB][RS_NT];
   rs_prefetch<NK>(rs_gr[0], wbase(1), bvoff, b);
   // ---- the layers' vectors -> LDS
 #pragma unroll
@@ -317,7 +301,7 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
   // ---- S0: X = LN0(x + hy[grp]) — a quarter wave per row, three rounds of 32 rows
   {
     const int l16 = tid & 15;
-    rs_u4 xv[3][3], hv[3][3];
+    u4 xv[3][3], hv[3][3];
 #pragma unroll
     for (int p = 0; p < 3; p++) {
       const int row = row0 + 32 * p + (tid >> 4), rr = row < E ? row : E - 1;
@@ -325,15 +309,15 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       const __half* hr = a.hy + (int64_t)a.grp[rr] * D;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        xv[p][k] = *reinterpret_cast<const rs_u4*>(xr + (l16 + 16 * k) * 8);
-        hv[p][k] = *reinterpret_cast<const rs_u4*>(hr + (l16 + 16 * k) * 8);
+        xv[p][k] = *reinterpret_cast<const u4*>(xr + (l16 + 16 * k) * 8);
+        hv[p][k] = *reinterpret_cast<const u4*>(hr + (l16 + 16 * k) * 8);
       }
     }
-    rs_u4 gm[3], bt[3];
+    u4 gm[3], bt[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      gm[k] = *reinterpret_cast<const rs_u4*>(a.ln0_g + (l16 + 16 * k) * 8);
-      bt[k] = *reinterpret_cast<const rs_u4*>(a.ln0_b + (l16 + 16 * k) * 8);
+      gm[k] = *reinterpret_cast<const u4*>(a.ln0_g + (l16 + 16 * k) * 8);
+      bt[k] = *reinterpret_cast<const u4*>(a.ln0_b + (l16 + 16 * k) * 8);
     }
 #pragma unroll
     for (int p = 0; p < 3; p++) {
@@ -343,24 +327,24 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        const rs_h8 xh = __builtin_bit_cast(rs_h8, xv[p][k]), hh = __builtin_bit_cast(rs_h8, hv[p][k]);
+        const h8 xh = __builtin_bit_cast(h8, xv[p][k]), hh = __builtin_bit_cast(h8, hv[p][k]);
 #pragma unroll
         for (int i = 0; i < 8; i++) { t[k][i] = (float)xh[i] + (float)hh[i]; s += t[k][i]; }
       }
-      const float mean = rs_row16_sum(s) / (float)D;
+      const float mean = row16_sum(s) / (float)D;
       float q = 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++)
 #pragma unroll
         for (int i = 0; i < 8; i++) { const float d = t[k][i] - mean; q += d * d; }
-      const float rstd = live ? rsqrtf(rs_row16_sum(q) / (float)D + a.eps0) : 0.f;
+      const float rstd = live ? rsqrtf(row16_sum(q) / (float)D + a.eps0) : 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        const rs_h8 g8 = __builtin_bit_cast(rs_h8, gm[k]), b8 = __builtin_bit_cast(rs_h8, bt[k]);
-        rs_h8 o;
+        const h8 g8 = __builtin_bit_cast(h8, gm[k]), b8 = __builtin_bit_cast(h8, bt[k]);
+        h8 o;
 #pragma unroll
         for (int i = 0; i < 8; i++) o[i] = (_Float16)((t[k][i] - mean) * rstd * (float)g8[i] + (float)b8[i]);
-        *reinterpret_cast<rs_u4*>(X + rloc * PITCH + (l16 + 16 * k) * 16) = __builtin_bit_cast(rs_u4, o);
+        *reinterpret_cast<u4*>(X + rloc * PITCH + (l16 + 16 * k) * 16) = __builtin_bit_cast(u4, o);
       }
     }
   }
@@ -371,26 +355,26 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
   const int colw = 48 * wv + 4 * kg;
   unsigned char* eX = X + mi * PITCH + colw * 2;                       // + 16 mt PITCH + 32 t: 8 bytes
   unsigned char* eR = R + mi * PITCH + colw * 2;
-  auto vec4 = [&](int off, int t) { return rs_cvt4(*reinterpret_cast<const rs_h4*>(vec + off + colw + 16 * t)); };
+  auto vec4 = [&](int off, int t) { return rs_cvt4(*reinterpret_cast<const h4*>(vec + off + colw + 16 * t)); };
 #pragma unroll
   for (int rep = 0; rep < 2; rep++) {
     const int o_gr = rep == 0 ? 0 : 1152, o_r2 = rep == 0 ? 768 : 1920;
-    rs_f4 acc[MT][RS_NT];
+    f4 acc[MT][RS_NT];
     // ---- R = relu(X Wr0 + br0)
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
     rs_kloop<MT, NK, PITCH, true>(arowX, rs_gr[rep], wbase(1), bvoff, b, acc, rs_r2[rep], wbase(0));
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
-      const rs_f4 bs = vec4(o_gr + D, t);
+      const f4 bs = vec4(o_gr + D, t);
 #pragma unroll
       for (int mt = 0; mt < MT; mt++) {
-        rs_f4 v = acc[mt][t] + bs;
+        f4 v = acc[mt][t] + bs;
 #pragma unroll
         for (int r = 0; r < 4; r++) v[r] = fmaxf(v[r], 0.f);
-        *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
+        *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
       }
     }
     __syncthreads();
@@ -398,30 +382,30 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
     rs_kloop<MT, NK, PITCH, true>(arowR, rs_r2[rep], wbase(0), bvoff, b, acc, rs_gr[rep], wbase(0));
     __syncthreads();
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
-      const rs_f4 bs = vec4(o_r2, t);
+      const f4 bs = vec4(o_r2, t);
 #pragma unroll
-      for (int mt = 0; mt < MT; mt++) *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
+      for (int mt = 0; mt < MT; mt++) *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
     }
     // ---- gate = X Wg + bg;  t = x + sigmoid(gate) res
 #pragma unroll
     for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-      for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+      for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
     if (rep == 0) rs_kloop<MT, NK, PITCH, true>(arowX, rs_gr[0], wbase(0), bvoff, b, acc, rs_gr[1], wbase(1));
     else rs_kloop<MT, NK, PITCH>(arowX, rs_gr[1], wbase(0), bvoff, b, acc);
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
-      const rs_f4 bs = vec4(o_gr, t);
+      const f4 bs = vec4(o_gr, t);
 #pragma unroll
       for (int mt = 0; mt < MT; mt++) {
         const int off = 16 * mt * PITCH + 32 * t;
-        const rs_f4 gv = rs_cvt4(rs_pack4(acc[mt][t] + bs));           // (rounded where the layer-by-layer path stores it)
-        const rs_f4 res = rs_cvt4(*reinterpret_cast<const rs_h4*>(eR + off)), xv = rs_cvt4(*reinterpret_cast<const rs_h4*>(eX + off));
+        const f4 gv = rs_cvt4(rs_pack4(acc[mt][t] + bs));           // (rounded where the layer-by-layer path stores it)
+        const f4 res = rs_cvt4(*reinterpret_cast<const h4*>(eR + off)), xv = rs_cvt4(*reinterpret_cast<const h4*>(eX + off));
 #pragma unroll
         for (int r = 0; r < 4; r++) acc[mt][t][r] = xv[r] + res[r] * __builtin_amdgcn_rcpf(1.0f + __expf(-gv[r]));
       }
@@ -431,11 +415,11 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       rs_row_stats<MT>(acc, part, stat, a.eps2, tid, wv, mi, kg);
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) {
-        const rs_f4 g = vec4(2304, t), bb = vec4(2688, t);
+        const f4 g = vec4(2304, t), bb = vec4(2688, t);
 #pragma unroll
         for (int mt = 0; mt < MT; mt++) {
           const float mean = stat[2 * (16 * mt + mi)], rstd = stat[2 * (16 * mt + mi) + 1];
-          *reinterpret_cast<rs_h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4((acc[mt][t] - mean) * rstd * g + bb);
+          *reinterpret_cast<h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4((acc[mt][t] - mean) * rstd * g + bb);
         }
       }
       __syncthreads();
@@ -443,18 +427,18 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
 #pragma unroll
       for (int t = 0; t < RS_NT; t++)
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) *reinterpret_cast<rs_h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t]);
+        for (int mt = 0; mt < MT; mt++) *reinterpret_cast<h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t]);
       __syncthreads();
     }
   }
   // ---- net out (whole rows) and the two heads on relu(net): a quarter wave per row
   {
     const int l16 = tid & 15;
-    rs_u4 wd0[3], wd1[3], ww0[3], ww1[3];
+    u4 wd0[3], wd1[3], ww0[3], ww1[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      wd0[k] = *reinterpret_cast<const rs_u4*>(a.Wd + (l16 + 16 * k) * 8); wd1[k] = *reinterpret_cast<const rs_u4*>(a.Wd + D + (l16 + 16 * k) * 8);
-      ww0[k] = *reinterpret_cast<const rs_u4*>(a.Ww + (l16 + 16 * k) * 8); ww1[k] = *reinterpret_cast<const rs_u4*>(a.Ww + D + (l16 + 16 * k) * 8);
+      wd0[k] = *reinterpret_cast<const u4*>(a.Wd + (l16 + 16 * k) * 8); wd1[k] = *reinterpret_cast<const u4*>(a.Wd + D + (l16 + 16 * k) * 8);
+      ww0[k] = *reinterpret_cast<const u4*>(a.Ww + (l16 + 16 * k) * 8); ww1[k] = *reinterpret_cast<const u4*>(a.Ww + D + (l16 + 16 * k) * 8);
     }
     const float bd0 = __half2float(a.bd[0]), bd1 = __half2float(a.bd[1]), bw0 = __half2float(a.bw[0]), bw1 = __half2float(a.bw[1]);
 #pragma unroll
@@ -464,16 +448,16 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
       float d0 = 0.f, d1 = 0.f, w0 = 0.f, w1 = 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        const rs_u4 v = *reinterpret_cast<const rs_u4*>(X + rloc * PITCH + (l16 + 16 * k) * 16);
+        const u4 v = *reinterpret_cast<const u4*>(X + rloc * PITCH + (l16 + 16 * k) * 16);
         if constexpr (OUT32) {
           if (live) {
-            const rs_h8 h8 = __builtin_bit_cast(rs_h8, v);
+            const h8 x8 = __builtin_bit_cast(h8, v);
             float* op_ = a.net_out32 + (int64_t)row * D + (l16 + 16 * k) * 8;
-            *reinterpret_cast<rs_f4*>(op_) = rs_f4{(float)h8[0], (float)h8[1], (float)h8[2], (float)h8[3]};
-            *reinterpret_cast<rs_f4*>(op_ + 4) = rs_f4{(float)h8[4], (float)h8[5], (float)h8[6], (float)h8[7]};
+            *reinterpret_cast<f4*>(op_) = f4{(float)x8[0], (float)x8[1], (float)x8[2], (float)x8[3]};
+            *reinterpret_cast<f4*>(op_ + 4) = f4{(float)x8[4], (float)x8[5], (float)x8[6], (float)x8[7]};
           }
         } else {
-          if (live) *reinterpret_cast<rs_u4*>(a.net_out + (int64_t)row * D + (l16 + 16 * k) * 8) = v;
+          if (live) *reinterpret_cast<u4*>(a.net_out + (int64_t)row * D + (l16 + 16 * k) * 8) = v;
         }
         // relu on fp16 pairs, products of fp16 pairs summed in fp32 (v_dot2_f32_f16: exact products, like the fp32 multiply-adds they replace)
         typedef _Float16 h2 __attribute__((ext_vector_type(2)));
@@ -487,7 +471,7 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
           w1 = __builtin_amdgcn_fdot2(u, __builtin_bit_cast(h2, c1), w1, false);
         }
       }
-      d0 = rs_row16_sum(d0); d1 = rs_row16_sum(d1); w0 = rs_row16_sum(w0); w1 = rs_row16_sum(w1);
+      d0 = row16_sum(d0); d1 = row16_sum(d1); w0 = row16_sum(w0); w1 = row16_sum(w1);
       if (live && l16 == 0) {
         a.delta[(int64_t)row * 2] = __float2half(d0 + bd0); a.delta[(int64_t)row * 2 + 1] = __float2half(d1 + bd1);
         a.weight[(int64_t)row * 2] = __float2half(1.0f / (1.0f + __expf(-(w0 + bw0))));
@@ -504,9 +488,9 @@ __global__ __launch_bounds__(512) void k_rs_gru_f16(RsGru a) {
 // FG: behind either, the 768-wide f | g layer of the NEXT SoftAgg (blocks.py:36-40) on the rows still in X: fg [M, 768], two more products.
 template <bool MLP, bool FG>
 __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ldx, int x_rows, const int64_t* __restrict__ gather,
-                                                      const rs_u4* __restrict__ w1, const __half* __restrict__ b1, const rs_u4* __restrict__ w2,
+                                                      const u4* __restrict__ w1, const __half* __restrict__ b1, const u4* __restrict__ w2,
                                                       const __half* __restrict__ b2, const __half* residual, __half* y, int M,
-                                                      const __half* __restrict__ hy, const int* __restrict__ grp, const rs_u4* __restrict__ wfg,
+                                                      const __half* __restrict__ hy, const int* __restrict__ grp, const u4* __restrict__ wfg,
                                                       const __half* __restrict__ bfg, __half* __restrict__ fg) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char rs_lds[];
   constexpr int MT = RG_MT, NK = RG_NK, PITCH = RG_PITCH, ROWS = RG_ROWS, D = 384, PPR = D / 8, AP = ROWS * PPR / 512;
@@ -516,45 +500,45 @@ __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ld
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS;
   const unsigned bvoff = (unsigned)lane * 16u;
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(w1), 0, (unsigned)(D * D * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(w2), 0, (unsigned)(D * D * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(w1), 0, (unsigned)(D * D * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(w2), 0, (unsigned)(D * D * 2), 0x00020000);
   const unsigned wbase = (unsigned)((wv * NK) * RS_NT * 1024);
-  const __amdgpu_buffer_rsrc_t rsfg = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(wfg), 0, FG ? (unsigned)(2 * D * D * 2) : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsfg = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(wfg), 0, FG ? (unsigned)(2 * D * D * 2) : 0u, 0x00020000);
   auto wbfg = [&](int nb) { return (unsigned)(((nb * RS_NW + wv) * NK) * RS_NT * 1024); };
   // ---- the (gathered) rows -> X
-  rs_u4 ap[AP];
+  u4 ap[AP];
 #pragma unroll
   for (int i = 0; i < AP; i++) {
     const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
     int64_t src = row0 + row < M ? ((MLP && gather) ? gather[row0 + row] : (int64_t)(row0 + row)) : -1;
     if (src >= x_rows) src = -1;
-    ap[i] = src >= 0 ? *reinterpret_cast<const rs_u4*>(x + src * ldx + 8 * c) : rs_u4{0u, 0u, 0u, 0u};
+    ap[i] = src >= 0 ? *reinterpret_cast<const u4*>(x + src * ldx + 8 * c) : u4{0u, 0u, 0u, 0u};
   }
-  rs_u4 b[RS_RB][RS_NT];
+  u4 b[RS_RB][RS_NT];
   if (MLP) rs_prefetch<NK>(rs1, wbase, bvoff, b);
   else if (FG) rs_prefetch<NK>(rsfg, wbfg(0), bvoff, b);
   if (!MLP) {                                                          // x + hy[grp], rounded as the expand-add kernel stores it, and back to y
-    rs_u4 hp[AP];
+    u4 hp[AP];
 #pragma unroll
     for (int i = 0; i < AP; i++) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-      hp[i] = row0 + row < M ? *reinterpret_cast<const rs_u4*>(hy + (int64_t)grp[row0 + row] * D + 8 * c) : rs_u4{0u, 0u, 0u, 0u};
+      hp[i] = row0 + row < M ? *reinterpret_cast<const u4*>(hy + (int64_t)grp[row0 + row] * D + 8 * c) : u4{0u, 0u, 0u, 0u};
     }
 #pragma unroll
     for (int i = 0; i < AP; i++) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-      const rs_h8 a8 = __builtin_bit_cast(rs_h8, ap[i]), h8 = __builtin_bit_cast(rs_h8, hp[i]);
-      rs_h8 o;
+      const h8 a8 = __builtin_bit_cast(h8, ap[i]), p8 = __builtin_bit_cast(h8, hp[i]);
+      h8 o;
 #pragma unroll
-      for (int e = 0; e < 8; e++) o[e] = (_Float16)((float)a8[e] + (float)h8[e]);
-      ap[i] = __builtin_bit_cast(rs_u4, o);
-      if (row0 + row < M) *reinterpret_cast<rs_u4*>(y + (int64_t)(row0 + row) * D + 8 * c) = ap[i];
+      for (int e = 0; e < 8; e++) o[e] = (_Float16)((float)a8[e] + (float)p8[e]);
+      ap[i] = __builtin_bit_cast(u4, o);
+      if (row0 + row < M) *reinterpret_cast<u4*>(y + (int64_t)(row0 + row) * D + 8 * c) = ap[i];
     }
   }
 #pragma unroll
   for (int i = 0; i < AP; i++) {
     const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-    *reinterpret_cast<rs_u4*>(X + row * PITCH + 16 * c) = ap[i];
+    *reinterpret_cast<u4*>(X + row * PITCH + 16 * c) = ap[i];
   }
   __syncthreads();
   const unsigned char* arowX = X + mi * PITCH + 16 * kg;
@@ -562,23 +546,23 @@ __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ld
   const int colw = 48 * wv + 4 * kg;
   unsigned char* eX = X + mi * PITCH + colw * 2;
   unsigned char* eR = R + mi * PITCH + colw * 2;
-  rs_f4 acc[MT][RS_NT];
+  f4 acc[MT][RS_NT];
   if (MLP) {
   // ---- R = relu(X W1 + b1)
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-    for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   rs_kloop<MT, NK, PITCH, true>(arowX, rs1, wbase, bvoff, b, acc, rs2, wbase);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 bs = rs_cvt4(*reinterpret_cast<const rs_h4*>(reinterpret_cast<const _Float16*>(b1) + colw + 16 * t));
+    const f4 bs = rs_cvt4(*reinterpret_cast<const h4*>(reinterpret_cast<const _Float16*>(b1) + colw + 16 * t));
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-      rs_f4 v = acc[mt][t] + bs;
+      f4 v = acc[mt][t] + bs;
 #pragma unroll
       for (int r = 0; r < 4; r++) v[r] = fmaxf(v[r], 0.f);
-      *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
+      *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
     }
   }
   __syncthreads();                                                     // R complete, everybody done with X
@@ -586,39 +570,39 @@ __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ld
 #pragma unroll
     for (int i = 0; i < AP; i++) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-      ap[i] = row0 + row < M ? *reinterpret_cast<const rs_u4*>(residual + (int64_t)(row0 + row) * D + 8 * c) : rs_u4{0u, 0u, 0u, 0u};
+      ap[i] = row0 + row < M ? *reinterpret_cast<const u4*>(residual + (int64_t)(row0 + row) * D + 8 * c) : u4{0u, 0u, 0u, 0u};
     }
   }
   // ---- y = R W2 + b2 [+ residual]
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-    for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   if (FG) rs_kloop<MT, NK, PITCH, true>(arowR, rs2, wbase, bvoff, b, acc, rsfg, wbfg(0));
   else rs_kloop<MT, NK, PITCH>(arowR, rs2, wbase, bvoff, b, acc);
   if (residual) {
 #pragma unroll
     for (int i = 0; i < AP; i++) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-      *reinterpret_cast<rs_u4*>(X + row * PITCH + 16 * c) = ap[i];
+      *reinterpret_cast<u4*>(X + row * PITCH + 16 * c) = ap[i];
     }
     __syncthreads();                                                   // the residual rows are in X
   }
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 bs = rs_cvt4(*reinterpret_cast<const rs_h4*>(reinterpret_cast<const _Float16*>(b2) + colw + 16 * t));
+    const f4 bs = rs_cvt4(*reinterpret_cast<const h4*>(reinterpret_cast<const _Float16*>(b2) + colw + 16 * t));
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-      rs_f4 v = acc[mt][t] + bs;
-      if (residual) v += rs_cvt4(*reinterpret_cast<const rs_h4*>(eX + 16 * mt * PITCH + 32 * t));
-      *reinterpret_cast<rs_h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
+      f4 v = acc[mt][t] + bs;
+      if (residual) v += rs_cvt4(*reinterpret_cast<const h4*>(eX + 16 * mt * PITCH + 32 * t));
+      *reinterpret_cast<h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
     }
   }
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < AP; i++) {
     const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-    if (row0 + row < M) *reinterpret_cast<rs_u4*>(y + (int64_t)(row0 + row) * D + 8 * c) = *reinterpret_cast<const rs_u4*>(X + row * PITCH + 16 * c);
+    if (row0 + row < M) *reinterpret_cast<u4*>(y + (int64_t)(row0 + row) * D + 8 * c) = *reinterpret_cast<const u4*>(X + row * PITCH + 16 * c);
   }
   }   // MLP
   if (FG) {
@@ -628,21 +612,21 @@ __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ld
 #pragma unroll
       for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-        for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+        for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
       if (nb == 0) rs_kloop<MT, NK, PITCH, true>(arowX, rsfg, wbfg(0), bvoff, b, acc, rsfg, wbfg(1));
       else rs_kloop<MT, NK, PITCH>(arowX, rsfg, wbfg(1), bvoff, b, acc);
       if (nb == 1) __syncthreads();                                    // the first half has left R
 #pragma unroll
       for (int t = 0; t < RS_NT; t++) {
-        const rs_f4 bs = rs_cvt4(*reinterpret_cast<const rs_h4*>(reinterpret_cast<const _Float16*>(bfg) + nb * D + colw + 16 * t));
+        const f4 bs = rs_cvt4(*reinterpret_cast<const h4*>(reinterpret_cast<const _Float16*>(bfg) + nb * D + colw + 16 * t));
 #pragma unroll
-        for (int mt = 0; mt < MT; mt++) *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
+        for (int mt = 0; mt < MT; mt++) *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
       }
       __syncthreads();
 #pragma unroll
       for (int i = 0; i < AP; i++) {
         const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-        if (row0 + row < M) *reinterpret_cast<rs_u4*>(fg + (int64_t)(row0 + row) * (2 * D) + nb * D + 8 * c) = *reinterpret_cast<const rs_u4*>(R + row * PITCH + 16 * c);
+        if (row0 + row < M) *reinterpret_cast<u4*>(fg + (int64_t)(row0 + row) * (2 * D) + nb * D + 8 * c) = *reinterpret_cast<const u4*>(R + row * PITCH + 16 * c);
       }
     }
   }
@@ -654,8 +638,8 @@ __global__ __launch_bounds__(512) void k_rs_mlp2_f16(const __half* x, int64_t ld
 // turns in R / X / R; the last LayerNorm runs row-wise (a quarter wave per row) with net and inp read as whole rows.
 struct RsCorr {
   const __half* corr; int64_t ldc;                                     // [E, 882], rows 4-byte aligned
-  const rs_u4* w0; const __half* b0; const rs_u4* w2; const __half* b2; const __half* ln3_g; const __half* ln3_b;
-  const rs_u4* w5; const __half* b5; const __half* net; const __half* inp; const __half* ln_g; const __half* ln_b; __half* out;
+  const u4* w0; const __half* b0; const u4* w2; const __half* b2; const __half* ln3_g; const __half* ln3_b;
+  const u4* w5; const __half* b5; const __half* net; const __half* inp; const __half* ln_g; const __half* ln_b; __half* out;
   int E, K0; float eps3, eps;
   const float* net32;                                                  // NET32 instantiation: the recurrent state as the caller holds it (autocast keeps it in fp32)
 };
@@ -677,12 +661,12 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   const int row0 = blockIdx.x * ROWS, E = a.E, K0 = a.K0;
   const unsigned bvoff = (unsigned)lane * 16u;
   const __amdgpu_buffer_rsrc_t rsc = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(a.corr), 0, rs_whole_dwords(((int64_t)(E - 1) * a.ldc + K0) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w0), 0, (unsigned)(D * NK0 * 32 * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w2), 0, (unsigned)(D * D * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs5 = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(a.w5), 0, (unsigned)(D * D * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(a.w0), 0, (unsigned)(D * NK0 * 32 * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(a.w2), 0, (unsigned)(D * D * 2), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs5 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(a.w5), 0, (unsigned)(D * D * 2), 0x00020000);
   const unsigned wb0 = (unsigned)((wv * NK0) * RS_NT * 1024), wb = (unsigned)((wv * NK) * RS_NT * 1024);
   // ---- chunks 0 and 1 of the rows -> X, R
-  rs_u4 ap[2][AP];
+  u4 ap[2][AP];
 #pragma unroll
   for (int ch = 0; ch < 2; ch++)
 #pragma unroll
@@ -690,7 +674,7 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
       ap[ch][i] = __builtin_amdgcn_raw_buffer_load_b128(rsc, row0 + row < E ? (unsigned)(((int64_t)(row0 + row) * a.ldc + 384 * ch + 8 * c) * 2) : OFF_NONE, 0, 0);
     }
-  rs_u4 b[RS_RB][RS_NT];
+  u4 b[RS_RB][RS_NT];
   rs_prefetch<NK>(rs0, wb0, bvoff, b);
 #pragma unroll
   for (int k = 0; k < (RC_VEC + 511) / 512; k++) {
@@ -705,10 +689,10 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
 #pragma unroll
     for (int i = 0; i < AP; i++) {
       const int p = tid + 512 * i, row = p / PPR, c = p - row * PPR;
-      *reinterpret_cast<rs_u4*>((ch ? R : X) + row * PITCH + 16 * c) = ap[ch][i];
+      *reinterpret_cast<u4*>((ch ? R : X) + row * PITCH + 16 * c) = ap[ch][i];
     }
   // the third chunk (inputs 768 .. 895; what lies behind input K0 is not part of the row) travels while the first two multiply
-  rs_u4 a2[AP2];
+  u4 a2[AP2];
 #pragma unroll
   for (int i = 0; i < AP2; i++) {
     const int p = tid + 512 * i, row = p >> 4, c = p & 15, k = 768 + 8 * c;
@@ -720,12 +704,12 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   const int colw = 48 * wv + 4 * kg;
   unsigned char* eX = X + mi * PITCH + colw * 2;
   unsigned char* eR = R + mi * PITCH + colw * 2;
-  auto vec4 = [&](int off, int t) { return rs_cvt4(*reinterpret_cast<const rs_h4*>(vec + off + colw + 16 * t)); };
-  rs_f4 acc[MT][RS_NT];
+  auto vec4 = [&](int off, int t) { return rs_cvt4(*reinterpret_cast<const h4*>(vec + off + colw + 16 * t)); };
+  f4 acc[MT][RS_NT];
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-    for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   // ---- h = relu(corr W0 + b0): 12 + 12 + 4 K steps
   rs_kloop<MT, NK, PITCH, true>(arowX, rs0, wb0, bvoff, b, acc, rs0, wb0 + 12u * RS_NT * 1024u);
   rs_kloop<MT, NK, PITCH, true>(arowR, rs0, wb0 + 12u * RS_NT * 1024u, bvoff, b, acc, rs0, wb0 + 24u * RS_NT * 1024u);
@@ -734,25 +718,25 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   for (int i = 0; i < AP2; i++) {
     const int p = tid + 512 * i, row = p >> 4, c = p & 15, k = 768 + 8 * c;
     if (k < K0 && k + 8 > K0) {
-      rs_h8 v = __builtin_bit_cast(rs_h8, a2[i]);
+      h8 v = __builtin_bit_cast(h8, a2[i]);
 #pragma unroll
       for (int e = 0; e < 8; e++) v[e] = k + e < K0 ? v[e] : (_Float16)0.f;
-      a2[i] = __builtin_bit_cast(rs_u4, v);
+      a2[i] = __builtin_bit_cast(u4, v);
     }
-    *reinterpret_cast<rs_u4*>(X + row * PITCH + 16 * c) = a2[i];
+    *reinterpret_cast<u4*>(X + row * PITCH + 16 * c) = a2[i];
   }
   __syncthreads();
   rs_kloop<MT, 4, PITCH, true>(arowX, rs0, wb0 + 24u * RS_NT * 1024u, bvoff, b, acc, rs2, wb);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 bs = vec4(0, t);
+    const f4 bs = vec4(0, t);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-      rs_f4 v = acc[mt][t] + bs;
+      f4 v = acc[mt][t] + bs;
 #pragma unroll
       for (int r = 0; r < 4; r++) v[r] = fmaxf(v[r], 0.f);
-      *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
-      acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
+      acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
     }
   }
   __syncthreads();
@@ -760,22 +744,22 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   rs_kloop<MT, NK, PITCH, true>(arowR, rs2, wb, bvoff, b, acc, rs5, wb);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 bs = vec4(384, t);
+    const f4 bs = vec4(384, t);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) acc[mt][t] = rs_cvt4(rs_pack4(acc[mt][t] + bs));      // (rounded where the layer-by-layer path stores it)
   }
   rs_row_stats<MT>(acc, part, stat, a.eps3, tid, wv, mi, kg);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 g = vec4(768, t), bb = vec4(1152, t);
+    const f4 g = vec4(768, t), bb = vec4(1152, t);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
       const float mean = stat[2 * (16 * mt + mi)], rstd = stat[2 * (16 * mt + mi) + 1];
-      rs_f4 v = (acc[mt][t] - mean) * rstd * g + bb;
+      f4 v = (acc[mt][t] - mean) * rstd * g + bb;
 #pragma unroll
       for (int r = 0; r < 4; r++) v[r] = fmaxf(v[r], 0.f);
-      *reinterpret_cast<rs_h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
-      acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+      *reinterpret_cast<h4*>(eX + 16 * mt * PITCH + 32 * t) = rs_pack4(v);
+      acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
     }
   }
   __syncthreads();
@@ -783,15 +767,15 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
   rs_kloop<MT, NK, PITCH>(arowX, rs5, wb, bvoff, b, acc);
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 bs = vec4(1536, t);
+    const f4 bs = vec4(1536, t);
 #pragma unroll
-    for (int mt = 0; mt < MT; mt++) *reinterpret_cast<rs_h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
+    for (int mt = 0; mt < MT; mt++) *reinterpret_cast<h4*>(eR + 16 * mt * PITCH + 32 * t) = rs_pack4(acc[mt][t] + bs);
   }
   __syncthreads();
   // ---- out = LN(net + inp + c): a quarter wave per row
   {
     const int l16 = tid & 15;
-    rs_u4 nv[3][3], nw[NET32 ? 3 : 1][3], iv[3][3];
+    u4 nv[3][3], nw[NET32 ? 3 : 1][3], iv[3][3];
 #pragma unroll
     for (int p = 0; p < 3; p++) {
       const int row = row0 + 32 * p + (tid >> 4), rr = row < E ? row : E - 1;
@@ -799,19 +783,19 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
       for (int k = 0; k < 3; k++) {
         if constexpr (NET32) {
           const float* np_ = a.net32 + (int64_t)rr * D + (l16 + 16 * k) * 8;
-          nv[p][k] = *reinterpret_cast<const rs_u4*>(np_);
-          nw[p][k] = *reinterpret_cast<const rs_u4*>(np_ + 4);
+          nv[p][k] = *reinterpret_cast<const u4*>(np_);
+          nw[p][k] = *reinterpret_cast<const u4*>(np_ + 4);
         } else {
-          nv[p][k] = *reinterpret_cast<const rs_u4*>(a.net + (int64_t)rr * D + (l16 + 16 * k) * 8);
+          nv[p][k] = *reinterpret_cast<const u4*>(a.net + (int64_t)rr * D + (l16 + 16 * k) * 8);
         }
-        iv[p][k] = *reinterpret_cast<const rs_u4*>(a.inp + (int64_t)rr * D + (l16 + 16 * k) * 8);
+        iv[p][k] = *reinterpret_cast<const u4*>(a.inp + (int64_t)rr * D + (l16 + 16 * k) * 8);
       }
     }
-    rs_u4 gm[3], bt[3];
+    u4 gm[3], bt[3];
 #pragma unroll
     for (int k = 0; k < 3; k++) {
-      gm[k] = *reinterpret_cast<const rs_u4*>(a.ln_g + (l16 + 16 * k) * 8);
-      bt[k] = *reinterpret_cast<const rs_u4*>(a.ln_b + (l16 + 16 * k) * 8);
+      gm[k] = *reinterpret_cast<const u4*>(a.ln_g + (l16 + 16 * k) * 8);
+      bt[k] = *reinterpret_cast<const u4*>(a.ln_b + (l16 + 16 * k) * 8);
     }
 #pragma unroll
     for (int p = 0; p < 3; p++) {
@@ -820,36 +804,36 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
       float s = 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++) {
-        const rs_h8 ih = __builtin_bit_cast(rs_h8, iv[p][k]),
-                    ch = __builtin_bit_cast(rs_h8, *reinterpret_cast<const rs_u4*>(R + rloc * PITCH + (l16 + 16 * k) * 16));
+        const h8 ih = __builtin_bit_cast(h8, iv[p][k]),
+                    ch = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(R + rloc * PITCH + (l16 + 16 * k) * 16));
         float xf[8];
         if constexpr (NET32) {
-          const rs_f4 lo4 = __builtin_bit_cast(rs_f4, nv[p][k]), hi4 = __builtin_bit_cast(rs_f4, nw[p][k]);
+          const f4 lo4 = __builtin_bit_cast(f4, nv[p][k]), hi4 = __builtin_bit_cast(f4, nw[p][k]);
 #pragma unroll
           for (int i = 0; i < 4; i++) { xf[i] = lo4[i]; xf[4 + i] = hi4[i]; }
         } else {
-          const rs_h8 xh = __builtin_bit_cast(rs_h8, nv[p][k]);
+          const h8 xh = __builtin_bit_cast(h8, nv[p][k]);
 #pragma unroll
           for (int i = 0; i < 8; i++) xf[i] = (float)xh[i];
         }
 #pragma unroll
         for (int i = 0; i < 8; i++) { t[k][i] = xf[i] + (float)ih[i] + (float)ch[i]; s += t[k][i]; }
       }
-      const float mean = rs_row16_sum(s) / (float)D;
+      const float mean = row16_sum(s) / (float)D;
       float q = 0.f;
 #pragma unroll
       for (int k = 0; k < 3; k++)
 #pragma unroll
         for (int i = 0; i < 8; i++) { const float d = t[k][i] - mean; q += d * d; }
-      const float rstd = rsqrtf(rs_row16_sum(q) / (float)D + a.eps);
+      const float rstd = rsqrtf(row16_sum(q) / (float)D + a.eps);
       if (row < E) {
 #pragma unroll
         for (int k = 0; k < 3; k++) {
-          const rs_h8 g8 = __builtin_bit_cast(rs_h8, gm[k]), b8 = __builtin_bit_cast(rs_h8, bt[k]);
-          rs_h8 o;
+          const h8 g8 = __builtin_bit_cast(h8, gm[k]), b8 = __builtin_bit_cast(h8, bt[k]);
+          h8 o;
 #pragma unroll
           for (int i = 0; i < 8; i++) o[i] = (_Float16)((t[k][i] - mean) * rstd * (float)g8[i] + (float)b8[i]);
-          *reinterpret_cast<rs_u4*>(a.out + (int64_t)row * D + (l16 + 16 * k) * 8) = __builtin_bit_cast(rs_u4, o);
+          *reinterpret_cast<u4*>(a.out + (int64_t)row * D + (l16 + 16 * k) * 8) = __builtin_bit_cast(u4, o);
         }
       }
     }
@@ -863,30 +847,6 @@ __global__ __launch_bounds__(512) void k_rs_corr_f16(RsCorr a) {
 // streams its hi and lo weight fragments into registers one K step ahead; three products per block.  The result goes through LDS (over
 // the row tiles) so that whole rows leave, with the ReLU adjoint mask and the residual read as whole rows too.  One workgroup = 96 rows x
 // 384 columns; a 768-wide layer = two column blocks (blockIdx.y) that split the rows again.
-__device__ __forceinline__ int rs_scale_exp(float m) {                 // biased exponent of the power of two that brings m into [2^8, 2^9)
-  int e = (int)((__float_as_uint(m) >> 23) & 255u);
-  e = e < 16 ? 16 : e;
-  return 127 + 8 + 127 - e;
-}
-__device__ __forceinline__ float rs_pow2(int biased) { return __uint_as_float((unsigned)(biased < 0 ? 0 : (biased > 254 ? 254 : biased)) << 23); }
-__device__ __forceinline__ void rs_split8(const float (&x)[8], rs_u4& hi, rs_u4& lo) {      // hi = rn(x), lo = rn(x - hi)
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h[j]) : "v"(x[2 * j]), "v"(x[2 * j + 1]));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l[j]) : "v"(h[j]), "v"(x[2 * j]));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l[j]) : "v"(h[j]), "v"(x[2 * j + 1]));
-  }
-  hi = rs_u4{h[0], h[1], h[2], h[3]};
-  lo = rs_u4{l[0], l[1], l[2], l[3]};
-}
-__device__ __forceinline__ float rs_row16_max(float v) {
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false)));
-  v = fmaxf(v, __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false)));
-  return v;
-}
 
 // W fp32 (element (n, k) at W[n * s_n + k * s_k]; N a multiple of 384) -> [N / 384][8 waves][ceil(K / 32)][3 tiles][hi | lo][64 lanes][16 B], every
 // column scaled by its power of two; then N floats: the inverse column scales.  Pass 1: the scales.
@@ -897,9 +857,9 @@ __global__ __launch_bounds__(256) void k_rs_wscale(const float* __restrict__ W, 
   for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(W[(int64_t)n * s_n + (int64_t)k * s_k]));
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if (lane == 0) inv[n] = rs_pow2(254 - rs_scale_exp(m));
+  if (lane == 0) inv[n] = pow2_biased(254 - scale_exp(m));
 }
-__global__ __launch_bounds__(256) void k_rs_wsplit(const float* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, rs_u4* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_rs_wsplit(const float* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, u4* __restrict__ out) {
   const int nk = (K + 31) / 32;
   const long long total = (long long)(N / RS_BN) * RS_NW * nk * RS_NT * 64;
   const float* inv = reinterpret_cast<const float*>(out + (size_t)total * 2);
@@ -910,13 +870,13 @@ __global__ __launch_bounds__(256) void k_rs_wsplit(const float* __restrict__ W, 
     const int s = (int)(r % nk); r /= nk;
     const int w = (int)(r % RS_NW), nb = (int)(r / RS_NW);
     const int n = nb * RS_BN + 48 * w + 16 * t + (lane & 15), k0 = 32 * s + 8 * (lane >> 4);
-    const float sc = rs_pow2(254 - (int)(__float_as_uint(inv[n]) >> 23));
+    const float sc = pow2_biased(254 - (int)(__float_as_uint(inv[n]) >> 23));
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = k0 + j < K ? W[(int64_t)n * s_n + (int64_t)(k0 + j) * s_k] * sc : 0.f;
-    rs_u4 hi, lo;
-    rs_split8(v, hi, lo);
-    rs_u4* dst = out + ((i >> 6) * 2) * 64 + lane;
+    u4 hi, lo;
+    split8(v, hi, lo);
+    u4* dst = out + ((i >> 6) * 2) * 64 + lane;
     dst[0] = hi;
     dst[64] = lo;
   }
@@ -926,7 +886,7 @@ constexpr int RF_YLD = 388;                                            // row pi
 constexpr int RF_LDS = 2 * RG_ROWS * RG_PITCH + RG_ROWS * 4 + 2 * 384 * 4;
 static_assert(RG_ROWS * RF_YLD * 4 <= 2 * RG_ROWS * RG_PITCH, "the result tile lies over the row tiles");
 
-__global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict__ x, int64_t ldx, const rs_u4* __restrict__ wimg, const float* __restrict__ bias,
+__global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict__ x, int64_t ldx, const u4* __restrict__ wimg, const float* __restrict__ bias,
                                                           const float* residual, const float* __restrict__ gate, float* y, int64_t ldy, int M, int N, int K,
                                                           int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char rs_lds[];
@@ -939,10 +899,10 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * ROWS, nb = blockIdx.y, NB = gridDim.y;
   const unsigned bvoff = (unsigned)lane * 16u;
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<rs_u4*>(wimg), 0, (unsigned)((int64_t)NB * RS_NW * NK * RS_NT * 2048), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(wimg), 0, (unsigned)((int64_t)NB * RS_NW * NK * RS_NT * 2048), 0x00020000);
   const unsigned wbase = (unsigned)(((nb * RS_NW + wv) * NK) * RS_NT * 2048);
   // this wave's weights: K step s, tile t = hi (1 KB) | lo (1 KB) at wbase + (s * 3 + t) * 2 KB; two steps in registers
-  rs_u4 bh[2][RS_NT], bl[2][RS_NT];
+  u4 bh[2][RS_NT], bl[2][RS_NT];
   auto load_b = [&](int s) {
 #pragma unroll
     for (int t = 0; t < RS_NT; t++) {
@@ -958,7 +918,7 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
   // ---- the rows: a quarter wave per row (16 lanes x 3 pieces of 8 floats), scaled by the row's own power of two, split, -> XH | XL
   {
     const int l16 = tid & 15;
-    rs_f4 xv[3][3][2];
+    f4 xv[3][3][2];
 #pragma unroll
     for (int p = 0; p < 3; p++) {
       const int row = row0 + 32 * p + (tid >> 4);
@@ -967,7 +927,7 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
       for (int k = 0; k < 3; k++) {
         const int c = (l16 + 16 * k) * 8;
 #pragma unroll
-        for (int h = 0; h < 2; h++) xv[p][k][h] = (c + 4 * h < K) ? *reinterpret_cast<const rs_f4*>(xr + c + 4 * h) : rs_f4{0.f, 0.f, 0.f, 0.f};
+        for (int h = 0; h < 2; h++) xv[p][k][h] = (c + 4 * h < K) ? *reinterpret_cast<const f4*>(xr + c + 4 * h) : f4{0.f, 0.f, 0.f, 0.f};
       }
     }
     load_b(0);
@@ -982,37 +942,37 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
         for (int h = 0; h < 2; h++)
 #pragma unroll
           for (int e = 0; e < 4; e++) m = fmaxf(m, fabsf(xv[p][k][h][e]));
-      m = rs_row16_max(m);
-      const int ex = rs_scale_exp(m);
-      const float sc = live ? rs_pow2(ex) : 0.f;
-      if (l16 == 0) rinv[rloc] = rs_pow2(254 - ex);
+      m = row16_max(m);
+      const int ex = scale_exp(m);
+      const float sc = live ? pow2_biased(ex) : 0.f;
+      if (l16 == 0) rinv[rloc] = pow2_biased(254 - ex);
 #pragma unroll
       for (int k = 0; k < 3; k++) {
         float v[8];
 #pragma unroll
         for (int e = 0; e < 4; e++) { v[e] = xv[p][k][0][e] * sc; v[4 + e] = xv[p][k][1][e] * sc; }
-        rs_u4 hi, lo;
-        rs_split8(v, hi, lo);
-        *reinterpret_cast<rs_u4*>(XH + rloc * PITCH + (l16 + 16 * k) * 16) = hi;
-        *reinterpret_cast<rs_u4*>(XL + rloc * PITCH + (l16 + 16 * k) * 16) = lo;
+        u4 hi, lo;
+        split8(v, hi, lo);
+        *reinterpret_cast<u4*>(XH + rloc * PITCH + (l16 + 16 * k) * 16) = hi;
+        *reinterpret_cast<u4*>(XL + rloc * PITCH + (l16 + 16 * k) * 16) = lo;
       }
     }
   }
   __syncthreads();
   const unsigned char* arH = XH + mi * PITCH + 16 * kg;
   const unsigned char* arL = XL + mi * PITCH + 16 * kg;
-  rs_f4 acc[MT][RS_NT];
+  f4 acc[MT][RS_NT];
 #pragma unroll
   for (int mt = 0; mt < MT; mt++)
 #pragma unroll
-    for (int t = 0; t < RS_NT; t++) acc[mt][t] = rs_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < RS_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   // ---- half steps: three row tiles at a time (their hi and lo fragments one half step ahead), the weights one K step ahead
   constexpr int HM = MT / 2;
-  rs_u4 ah[2][HM], al[2][HM];
+  u4 ah[2][HM], al[2][HM];
 #pragma unroll
   for (int u = 0; u < HM; u++) {
-    ah[0][u] = *reinterpret_cast<const rs_u4*>(arH + 16 * u * PITCH);
-    al[0][u] = *reinterpret_cast<const rs_u4*>(arL + 16 * u * PITCH);
+    ah[0][u] = *reinterpret_cast<const u4*>(arH + 16 * u * PITCH);
+    al[0][u] = *reinterpret_cast<const u4*>(arL + 16 * u * PITCH);
   }
 #pragma unroll
   for (int h = 0; h < 2 * NK; h++) {
@@ -1021,8 +981,8 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
       const int s1 = (h + 1) >> 1, hf1 = (h + 1) & 1;
 #pragma unroll
       for (int u = 0; u < HM; u++) {
-        ah[(h + 1) & 1][u] = *reinterpret_cast<const rs_u4*>(arH + 16 * (HM * hf1 + u) * PITCH + 64 * s1);
-        al[(h + 1) & 1][u] = *reinterpret_cast<const rs_u4*>(arL + 16 * (HM * hf1 + u) * PITCH + 64 * s1);
+        ah[(h + 1) & 1][u] = *reinterpret_cast<const u4*>(arH + 16 * (HM * hf1 + u) * PITCH + 64 * s1);
+        al[(h + 1) & 1][u] = *reinterpret_cast<const u4*>(arL + 16 * (HM * hf1 + u) * PITCH + 64 * s1);
       }
     }
     if (hf == 0 && s + 1 < NK) load_b(s + 1);
@@ -1031,30 +991,30 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
     for (int u = 0; u < HM; u++)                                       // small terms first; the same accumulator again 9 products later
 #pragma unroll
       for (int t = 0; t < RS_NT; t++)
-        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, bl[s & 1][t]), __builtin_bit_cast(rs_h8, ah[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
+        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, bl[s & 1][t]), __builtin_bit_cast(h8, ah[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
 #pragma unroll
     for (int u = 0; u < HM; u++)
 #pragma unroll
       for (int t = 0; t < RS_NT; t++)
-        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, bh[s & 1][t]), __builtin_bit_cast(rs_h8, al[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
+        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, bh[s & 1][t]), __builtin_bit_cast(h8, al[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
 #pragma unroll
     for (int u = 0; u < HM; u++)
 #pragma unroll
       for (int t = 0; t < RS_NT; t++)
-        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(rs_h8, bh[s & 1][t]), __builtin_bit_cast(rs_h8, ah[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
+        acc[HM * hf + u][t] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(h8, bh[s & 1][t]), __builtin_bit_cast(h8, ah[h & 1][u]), acc[HM * hf + u][t], 0, 0, 0);
     __builtin_amdgcn_sched_barrier(0);
   }
   __syncthreads();                                                     // everybody is done with the row tiles: the result tile takes their place
   const int colw = 48 * wv + 4 * kg;
 #pragma unroll
   for (int t = 0; t < RS_NT; t++) {
-    const rs_f4 ci = *reinterpret_cast<const rs_f4*>(cvec + colw + 16 * t), bs = *reinterpret_cast<const rs_f4*>(cvec + D + colw + 16 * t);
+    const f4 ci = *reinterpret_cast<const f4*>(cvec + colw + 16 * t), bs = *reinterpret_cast<const f4*>(cvec + D + colw + 16 * t);
 #pragma unroll
     for (int mt = 0; mt < MT; mt++) {
-      rs_f4 v = acc[mt][t] * rinv[16 * mt + mi] * ci + bs;
+      f4 v = acc[mt][t] * rinv[16 * mt + mi] * ci + bs;
 #pragma unroll
       for (int r = 0; r < 4; r++) v[r] = nb * D + colw + 16 * t + r >= relu_from ? fmaxf(v[r], 0.f) : v[r];
-      *reinterpret_cast<rs_f4*>(Y + (16 * mt + mi) * RF_YLD + colw + 16 * t) = v;
+      *reinterpret_cast<f4*>(Y + (16 * mt + mi) * RF_YLD + colw + 16 * t) = v;
     }
   }
   __syncthreads();
@@ -1063,15 +1023,15 @@ __global__ __launch_bounds__(512) void k_rs_linear_split(const float* __restrict
   for (int i = 0; i < YP; i++) {
     const int p = tid + 512 * i, row = p / (D / 4), c = p - row * (D / 4);
     if (row0 + row < M) {
-      rs_f4 v = *reinterpret_cast<const rs_f4*>(Y + row * RF_YLD + 4 * c);
+      f4 v = *reinterpret_cast<const f4*>(Y + row * RF_YLD + 4 * c);
       const int64_t o = (int64_t)(row0 + row) * ldy + nb * D + 4 * c;
       if (gate) {                                                      // a ReLU's output: this gradient passes where it did not clip
-        const rs_f4 q = *reinterpret_cast<const rs_f4*>(gate + o);
+        const f4 q = *reinterpret_cast<const f4*>(gate + o);
 #pragma unroll
         for (int r = 0; r < 4; r++) v[r] = q[r] > 0.f ? v[r] : 0.f;
       }
-      if (residual) v += *reinterpret_cast<const rs_f4*>(residual + o);     // (may be y itself: read, then written, by this thread)
-      *reinterpret_cast<rs_f4*>(y + o) = v;
+      if (residual) v += *reinterpret_cast<const f4*>(residual + o);     // (may be y itself: read, then written, by this thread)
+      *reinterpret_cast<f4*>(y + o) = v;
     }
   }
 }
@@ -1087,7 +1047,7 @@ static int rs_launch(const void* x, int64_t ldx, const void* wimg, const void* b
     DEVO_REQUIRE(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_rs_linear_f16<MT, NK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess,
                  "devo_upd_rs_linear_f16: cannot raise the dynamic LDS limit");
   }
-  hipLaunchKernelGGL((k_rs_linear_f16<MT, NK>), dim3((unsigned)((M + ROWS - 1) / ROWS)), dim3(512), lds, stream, (const __half*)x, ldx, (const rs_u4*)wimg,
+  hipLaunchKernelGGL((k_rs_linear_f16<MT, NK>), dim3((unsigned)((M + ROWS - 1) / ROWS)), dim3(512), lds, stream, (const __half*)x, ldx, (const u4*)wimg,
                      (const __half*)bias, (const __half*)residual, (__half*)y, ldy, M, NB, K, relu_from);
   return check_launch("devo_upd_rs_linear_f16");
 }
@@ -1101,8 +1061,8 @@ static int rs_chain_launch(const void* x, int64_t ldx, int x_rows, const int64_t
                  "devo_upd_rs_mlp2_f16: cannot raise the dynamic LDS limit");
   }
   hipLaunchKernelGGL((k_rs_mlp2_f16<MLP, FG>), dim3((unsigned)((M + RG_ROWS - 1) / RG_ROWS)), dim3(512), 2 * RG_ROWS * RG_PITCH, stream, (const __half*)x, ldx, x_rows, gather,
-                     (const rs_u4*)w1img, (const __half*)b1, (const rs_u4*)w2img, (const __half*)b2, (const __half*)residual, (__half*)y, M, (const __half*)hy, grp,
-                     (const rs_u4*)wfg, (const __half*)bfg, (__half*)fg);
+                     (const u4*)w1img, (const __half*)b1, (const u4*)w2img, (const __half*)b2, (const __half*)residual, (__half*)y, M, (const __half*)hy, grp,
+                     (const u4*)wfg, (const __half*)bfg, (__half*)fg);
   return check_launch("devo_upd_rs_mlp2_f16");
 }
 
@@ -1122,7 +1082,7 @@ int devo_upd_rs_pack_weight_f16(const void* W, int64_t s_n, int64_t s_k, int N, 
   DEVO_REQUIRE(W && img && N > 0 && K > 0 && N % RS_BN == 0, "devo_upd_rs_pack_weight_f16: N (%d) must be a multiple of 384", N);
   const long long total = (long long)N * ((K + 31) / 32) * 4;
   hipLaunchKernelGGL(k_rs_pack_f16, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const __half*)W, s_n, s_k, N, K,
-                     (rs_u4*)img);
+                     (u4*)img);
   return check_launch("devo_upd_rs_pack_weight_f16");
 }
 
@@ -1172,8 +1132,8 @@ static int rs_gru_impl(const void* x, const void* hy, const int* group_of, const
   }
   RsGru a;
   a.x = (const __half*)x; a.hy = (const __half*)hy; a.grp = group_of; a.ln0_g = (const __half*)ln0_w; a.ln0_b = (const __half*)ln0_b;
-  a.w_gr[0] = (const rs_u4*)wgr1_img; a.b_gr[0] = (const __half*)bgr1; a.w_r2[0] = (const rs_u4*)wr2_1_img; a.b_r2[0] = (const __half*)br2_1;
-  a.w_gr[1] = (const rs_u4*)wgr3_img; a.b_gr[1] = (const __half*)bgr3; a.w_r2[1] = (const rs_u4*)wr2_3_img; a.b_r2[1] = (const __half*)br2_3;
+  a.w_gr[0] = (const u4*)wgr1_img; a.b_gr[0] = (const __half*)bgr1; a.w_r2[0] = (const u4*)wr2_1_img; a.b_r2[0] = (const __half*)br2_1;
+  a.w_gr[1] = (const u4*)wgr3_img; a.b_gr[1] = (const __half*)bgr3; a.w_r2[1] = (const u4*)wr2_3_img; a.b_r2[1] = (const __half*)br2_3;
   a.ln2_g = (const __half*)ln2_w; a.ln2_b = (const __half*)ln2_b; a.Wd = (const __half*)Wd; a.bd = (const __half*)bd; a.Ww = (const __half*)Ww; a.bw = (const __half*)bw;
   a.net_out = out32 ? nullptr : (__half*)net_out; a.net_out32 = out32 ? (float*)net_out : nullptr;
   a.delta = (__half*)delta; a.weight = (__half*)weight; a.E = E; a.eps0 = eps0; a.eps2 = eps2;
@@ -1248,8 +1208,8 @@ static int rs_corr_impl(const void* corr, int64_t ldc, int K0, const void* w0img
                  "devo_upd_rs_corr_f16: cannot raise the dynamic LDS limit");
   }
   RsCorr a;
-  a.corr = (const __half*)corr; a.ldc = ldc; a.w0 = (const rs_u4*)w0img; a.b0 = (const __half*)b0; a.w2 = (const rs_u4*)w2img; a.b2 = (const __half*)b2;
-  a.ln3_g = (const __half*)ln3_w; a.ln3_b = (const __half*)ln3_b; a.w5 = (const rs_u4*)w5img; a.b5 = (const __half*)b5;
+  a.corr = (const __half*)corr; a.ldc = ldc; a.w0 = (const u4*)w0img; a.b0 = (const __half*)b0; a.w2 = (const u4*)w2img; a.b2 = (const __half*)b2;
+  a.ln3_g = (const __half*)ln3_w; a.ln3_b = (const __half*)ln3_b; a.w5 = (const u4*)w5img; a.b5 = (const __half*)b5;
   a.net = net32 ? nullptr : (const __half*)net; a.net32 = net32 ? (const float*)net : nullptr;
   a.inp = (const __half*)inp; a.ln_g = (const __half*)ln_w; a.ln_b = (const __half*)ln_b; a.out = (__half*)out; a.E = E; a.K0 = K0; a.eps3 = eps3; a.eps = eps;
   if (net32) hipLaunchKernelGGL(k_rs_corr_f16<true>, dim3((unsigned)((E + RG_ROWS - 1) / RG_ROWS)), dim3(512), RC_LDS, (hipStream_t)stream, a);
@@ -1280,7 +1240,7 @@ int devo_upd_rs_split_weight(const float* W, int64_t s_n, int64_t s_k, int N, in
   float* inv = reinterpret_cast<float*>(static_cast<unsigned char*>(img) + (size_t)N * ((K + 31) / 32 * 32) * 4);
   hipLaunchKernelGGL(k_rs_wscale, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, N, K, inv);
   const long long total = (long long)N * ((K + 31) / 32) * 4;
-  hipLaunchKernelGGL(k_rs_wsplit, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, N, K, (rs_u4*)img);
+  hipLaunchKernelGGL(k_rs_wsplit, dim3((unsigned)std::min<long long>((total + 255) / 256, 4096)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, N, K, (u4*)img);
   return check_launch("devo_upd_rs_split_weight");
 }
 int devo_upd_rs_split_supported(int N, int K) { return N > 0 && N % RS_BN == 0 && K > 352 && K <= 384 && K % 4 == 0; }
@@ -1298,7 +1258,7 @@ int devo_upd_rs_linear_split(const float* x, int64_t ldx, const void* wimg, cons
                  "devo_upd_rs_linear_split: cannot raise the dynamic LDS limit");
   }
   hipLaunchKernelGGL(k_rs_linear_split, dim3((unsigned)((M + RG_ROWS - 1) / RG_ROWS), (unsigned)(N / RS_BN)), dim3(512), RF_LDS, (hipStream_t)stream, x, ldx,
-                     (const rs_u4*)wimg, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
+                     (const u4*)wimg, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
   return check_launch("devo_upd_rs_linear_split");
 }
 

@@ -25,14 +25,11 @@
 // rows leave as whole 16-byte pieces, scaled back, with bias, ReLU (from a given column on) and an optional residual applied.
 // 53 760 B of LDS and 106 VGPRs: three workgroups per CU.  k_linear_f16 at the end of the file is the same shape for fp16 storage.
 #include "common.h"
+#include "f16split.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 
 namespace devo {
-
-typedef _Float16 ln_h8 __attribute__((ext_vector_type(8)));
-typedef float ln_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned ln_u4 __attribute__((ext_vector_type(4)));
 
 constexpr int LN_NT = 6;                          // column tiles of 16 per workgroup (96 columns)
 constexpr int LN_MT = 2;                          // row tiles of 16 per wave
@@ -46,30 +43,6 @@ constexpr int LN_RING = (LN_NSTAGE * LN_STAGE > 4 * LN_TILE_BYTES) ? LN_NSTAGE *
 constexpr int LN_SLAB = LN_MT * 16 * 128;         // one wave's activations of one K step: 32 rows x 128 bytes
 constexpr int LN_AUX = LN_RING + 4 * LN_SLAB;     // behind the ring and the four slabs:
 constexpr int LN_LDS = LN_AUX + 4 * LN_MT * 16 * 4;   // one float per row and wave (rescale factors, then the inverse row scales): 53 760 B = 42 granules of 1 280 B, three workgroups per CU
-constexpr int LN_EXP_TARGET = 8;                  // a scale puts its reference magnitude into [2^8, 2^9)
-constexpr float LN_RAISE = 16384.f;               // ... and is raised when a scaled value exceeds 2^14 (fp16's largest: 65504)
-
-// 8 fp32 values -> fp16 hi (8) and lo (8): hi = rn(x), lo = rn(x - hi)
-__device__ __forceinline__ void ln_split8(const float (&x)[8], ln_h8& hi, ln_h8& lo) {
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h[j]) : "v"(x[2 * j]), "v"(x[2 * j + 1]));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l[j]) : "v"(h[j]), "v"(x[2 * j]));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l[j]) : "v"(h[j]), "v"(x[2 * j + 1]));
-  }
-  const ln_u4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
-  hi = __builtin_bit_cast(ln_h8, hv);
-  lo = __builtin_bit_cast(ln_h8, lv);
-}
-
-// biased exponent of the power of two that brings magnitude m into [2^TARGET, 2^(TARGET+1))
-__device__ __forceinline__ int ln_scale_exp(float m) {
-  int e = (int)((__float_as_uint(m) >> 23) & 255u);
-  e = e < 16 ? 16 : e;                             // zero / tiny reference: a finite scale (2^(8 + 111))
-  return 127 + LN_EXP_TARGET + 127 - e;            // in [16, 246]
-}
-__device__ __forceinline__ float ln_pow2(int biased) { return __uint_as_float((unsigned)(biased < 0 ? 0 : (biased > 254 ? 254 : biased)) << 23); }
 
 // W (element (n, k) at W[n * s_n + k * s_k]: the forward's weight [N, K], or its transpose view for dX = dY W) -> the B-operand image
 // [N / 96][K / 32][6 tiles][hi | lo][64 lanes][16 B]: lane (n, kg) of tile t holds k = 32 s + 8 kg .. + 7 of column 96 nb + 16 t + n,
@@ -83,10 +56,10 @@ __global__ __launch_bounds__(256) void k_weight_scales(const float* __restrict__
     for (int k = lane; k < K; k += 64) m = fmaxf(m, fabsf(W[(int64_t)n * s_n + (int64_t)k * s_k]));
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if (lane == 0) inv[n] = ln_pow2(254 - ln_scale_exp(m));
+  if (lane == 0) inv[n] = pow2_biased(254 - scale_exp(m));
 }
 
-__global__ __launch_bounds__(256) void k_split_weight(const float* __restrict__ W, int64_t s_n, int64_t s_k, int N, int n_real, int K, ln_u4* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_split_weight(const float* __restrict__ W, int64_t s_n, int64_t s_k, int N, int n_real, int K, u4* __restrict__ out) {
   const int nk = (K + 31) / 32;
   const long long total = (long long)(N / LN_BN) * nk * LN_NT * 64;
   const float* inv = reinterpret_cast<const float*>(out) + (size_t)N * nk * 32;
@@ -97,30 +70,22 @@ __global__ __launch_bounds__(256) void k_split_weight(const float* __restrict__ 
     const long long r2 = r / LN_NT;
     const int s = (int)(r2 % nk), nb = (int)(r2 / nk);
     const int n = nb * LN_BN + 16 * t + (lane & 15), kg = lane >> 4, k0 = 32 * s + 8 * kg;
-    const float sc = ln_pow2(254 - (int)(__float_as_uint(inv[n]) >> 23));      // the reciprocal of a power of two
+    const float sc = pow2_biased(254 - (int)(__float_as_uint(inv[n]) >> 23));      // the reciprocal of a power of two
     float v[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) v[j] = (k0 + j < K && n < n_real) ? W[(int64_t)n * s_n + (int64_t)(k0 + j) * s_k] * sc : 0.f;      // (K rounded up to whole steps, N to whole blocks: zeros)
-    ln_h8 hi, lo;
-    ln_split8(v, hi, lo);
-    ln_u4* dst = out + ((r2 * LN_NT + t) * 2) * 64 + lane;
-    dst[0] = __builtin_bit_cast(ln_u4, hi);
-    dst[64] = __builtin_bit_cast(ln_u4, lo);
+    h8 hi, lo;
+    split8(v, hi, lo);
+    u4* dst = out + ((r2 * LN_NT + t) * 2) * 64 + lane;
+    dst[0] = __builtin_bit_cast(u4, hi);
+    dst[64] = __builtin_bit_cast(u4, lo);
   }
-}
-
-// LDS-DMA: 16 bytes per lane from (descriptor, per-lane offset, scalar offset) to lds_addr + 16 * lane; hipcc's waitcnt insertion does
-// not know it (the loop counts its own vmcnt before the barrier)
-__device__ __forceinline__ void ln_dma16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned lds_addr) {
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rs), "s"(lds_addr), "s"(soff) : "memory");
 }
 
 // y[M, N] = act(x[M, K] B + bias), B = the split weight image.  grid = 8 * ceil(row blocks / 8) * (N / 96), one row block's column
 // blocks on one XCD.
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_linear_split(
-    const float* __restrict__ x, int64_t ldx, const ln_u4* __restrict__ wsplit, const float* __restrict__ bias, const float* residual,
+    const float* __restrict__ x, int64_t ldx, const u4* __restrict__ wsplit, const float* __restrict__ bias, const float* residual,
     const float* __restrict__ gate, float* y, int64_t ldy, int M, int N, int K, int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char ln_lds[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
@@ -130,7 +95,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   if (rb * LN_BM >= M) return;
   constexpr unsigned OFF_NONE = 0x80000000u;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(x), 0, (unsigned)(((int64_t)(M - 1) * ldx + K) * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<ln_u4*>(wsplit), 0, (unsigned)((int64_t)Np * nk * 128), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(wsplit), 0, (unsigned)((int64_t)Np * nk * 128), 0x00020000);
   const int row_w = rb * LN_BM + LN_MT * 16 * wv;                     // this wave's first row
   // Activations: each wave brings its own 32 rows x 32 floats of a K step into its LDS slab by lane-linear DMA — eight lanes per row, a
   // quad of lanes inside one 128-byte line (16 addresser cycles per KB; 16 bytes per lane at a row stride cost 64) — and reads them back
@@ -164,19 +129,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int q = 0; q < LN_NT * 2 / 4; q++) {
       const int piece = wv + 4 * q;
-      ln_dma16(voff, rsw, (unsigned)(((nb * nk + s) * (LN_NT * 2) + piece) * 1024), lds0 + (unsigned)(buf * LN_STAGE + piece * 1024));
+      lds_dma16(voff, rsw, (unsigned)(((nb * nk + s) * (LN_NT * 2) + piece) * 1024), lds0 + (unsigned)(buf * LN_STAGE + piece * 1024));
     }
   };
   auto load_a = [&](int s) {                                         // K step s of this wave's rows -> its slab
 #pragma unroll
     for (int q = 0; q < 4; q++)
-      ln_dma16(s < nk ? avoff[q] : OFF_NONE, rsx, (unsigned)s * 128u, lds0 + (unsigned)(LN_RING + wv * LN_SLAB + q * 1024));
+      lds_dma16(s < nk ? avoff[q] : OFF_NONE, rsx, (unsigned)s * 128u, lds0 + (unsigned)(LN_RING + wv * LN_SLAB + q * 1024));
   };
-  ln_f4 acc[LN_MT][LN_NT];
+  f4 acc[LN_MT][LN_NT];
 #pragma unroll
   for (int mt = 0; mt < LN_MT; mt++)
 #pragma unroll
-    for (int t = 0; t < LN_NT; t++) acc[mt][t] = ln_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < LN_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   int esc[LN_MT];                                                     // biased exponent of each row's scale
   float sc[LN_MT];
 #pragma unroll
@@ -190,11 +155,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 
   auto step = [&](int s) {
     // this step's activations out of the slab, then the slab is free for the next step's (requested one step ahead; the weight pieces two)
-    ln_u4 cur[LN_MT][2];
+    u4 cur[LN_MT][2];
 #pragma unroll
     for (int mt = 0; mt < LN_MT; mt++)
 #pragma unroll
-      for (int h = 0; h < 2; h++) cur[mt][h] = *reinterpret_cast<const ln_u4*>(slab + aslot[mt][h]);
+      for (int h = 0; h < 2; h++) cur[mt][h] = *reinterpret_cast<const u4*>(slab + aslot[mt][h]);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     load_a(s + 1);
     stage(s + 2);
@@ -214,7 +179,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
       m = fmaxf(fmaxf(m, fabsf(xv[mt][3])), fabsf(xv[mt][4]));
       m = fmaxf(fmaxf(m, fabsf(xv[mt][5])), fmaxf(fabsf(xv[mt][6]), fabsf(xv[mt][7])));
       mx[mt] = m;
-      raise = raise || !(m * sc[mt] <= LN_RAISE);                     // (also: NaN)
+      raise = raise || !(m * sc[mt] <= F16_SPLIT_RAISE);                     // (also: NaN)
     }
     if (s == 0 || __builtin_amdgcn_ballot_w64(raise) != 0ull) {      // rare after the first step: new scales, accumulators follow
 #pragma unroll
@@ -222,41 +187,39 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         float m = mx[mt];
         m = fmaxf(m, __shfl_xor(m, 16));
         m = fmaxf(m, __shfl_xor(m, 32));
-        const bool need = s == 0 || !(m * sc[mt] <= LN_RAISE);
-        const int e_new = need ? ln_scale_exp(m) : esc[mt];
-        if (kg == 0) rowf[16 * mt + mi] = s == 0 ? 1.f : ln_pow2(127 + e_new - esc[mt]);
+        const bool need = s == 0 || !(m * sc[mt] <= F16_SPLIT_RAISE);
+        const int e_new = need ? scale_exp(m) : esc[mt];
+        if (kg == 0) rowf[16 * mt + mi] = s == 0 ? 1.f : pow2_biased(127 + e_new - esc[mt]);
         esc[mt] = e_new;
-        sc[mt] = ln_pow2(e_new);
+        sc[mt] = pow2_biased(e_new);
       }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_handoff();
       if (s != 0) {
 #pragma unroll
         for (int mt = 0; mt < LN_MT; mt++) {
-          const ln_f4 f = *reinterpret_cast<const ln_f4*>(rowf + 16 * mt + 4 * kg);
+          const f4 f = *reinterpret_cast<const f4*>(rowf + 16 * mt + 4 * kg);
 #pragma unroll
           for (int t = 0; t < LN_NT; t++) acc[mt][t] *= f;
         }
       }
       __builtin_amdgcn_wave_barrier();
     }
-    ln_h8 ah[LN_MT], al[LN_MT];
+    h8 ah[LN_MT], al[LN_MT];
 #pragma unroll
     for (int mt = 0; mt < LN_MT; mt++) {
 #pragma unroll
       for (int j = 0; j < 8; j++) xv[mt][j] *= sc[mt];
-      ln_split8(xv[mt], ah[mt], al[mt]);
+      split8(xv[mt], ah[mt], al[mt]);
     }
-    const ln_u4* sb = reinterpret_cast<const ln_u4*>(ln_lds + (s % LN_NSTAGE) * LN_STAGE) + lane;
+    const u4* sb = reinterpret_cast<const u4*>(ln_lds + (s % LN_NSTAGE) * LN_STAGE) + lane;
     __builtin_amdgcn_sched_barrier(0);                                 // the products start behind the split (interleaved: 8 more VGPRs)
 #pragma unroll
     for (int tg = 0; tg < LN_NT; tg += 3) {
-      ln_h8 bh[3], bl[3];
+      h8 bh[3], bl[3];
 #pragma unroll
       for (int u = 0; u < 3; u++) {
-        bh[u] = __builtin_bit_cast(ln_h8, sb[((tg + u) * 2 + 0) * 64]);
-        bl[u] = __builtin_bit_cast(ln_h8, sb[((tg + u) * 2 + 1) * 64]);
+        bh[u] = __builtin_bit_cast(h8, sb[((tg + u) * 2 + 0) * 64]);
+        bl[u] = __builtin_bit_cast(h8, sb[((tg + u) * 2 + 1) * 64]);
       }
 #pragma unroll
       for (int u = 0; u < 3; u++)                                      // small terms first; the same accumulator again 6 MFMAs later
@@ -287,19 +250,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   const bool vec_out = (ldy & 3) == 0 && ((reinterpret_cast<uintptr_t>(y) | reinterpret_cast<uintptr_t>(residual) | reinterpret_cast<uintptr_t>(gate)) & 15) == 0;
 #pragma unroll
   for (int mt = 0; mt < LN_MT; mt++) {
-    if (kg == 0) rowf[16 * mt + mi] = ln_pow2(254 - esc[mt]);
+    if (kg == 0) rowf[16 * mt + mi] = pow2_biased(254 - esc[mt]);
 #pragma unroll
     for (int t = 0; t < LN_NT; t++)
 #pragma unroll
       for (int r = 0; r < 4; r++) tile[(4 * kg + r) * LN_EPI_LD + 16 * t + mi] = acc[mt][t][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
 #pragma unroll
     for (int it = 0; it < 16 * PPR / 64; it++) {
       const int idx = it * 64 + lane, r = idx / PPR, c4 = idx - r * PPR;
-      ln_f4 v = *reinterpret_cast<const ln_f4*>(tile + r * LN_EPI_LD + 4 * c4);
-      v = v * rowf[16 * mt + r] * *reinterpret_cast<const ln_f4*>(colf + 4 * c4) + *reinterpret_cast<const ln_f4*>(colf + LN_BN + 4 * c4);
+      f4 v = *reinterpret_cast<const f4*>(tile + r * LN_EPI_LD + 4 * c4);
+      v = v * rowf[16 * mt + r] * *reinterpret_cast<const f4*>(colf + 4 * c4) + *reinterpret_cast<const f4*>(colf + LN_BN + 4 * c4);
       if (col0 + 4 * c4 >= relu_from) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
       const int row = row_w + 16 * mt + r, col = col0 + 4 * c4;
       if (row < M && col < N) {
@@ -308,11 +269,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
         const float* gt = gate ? gate + (int64_t)row * ldy + col : nullptr;      // a ReLU's output: this gradient passes where it did not clip
         if (vec_out && col + 4 <= N) {
           if (gt) {
-            const ln_f4 q = *reinterpret_cast<const ln_f4*>(gt);
+            const f4 q = *reinterpret_cast<const f4*>(gt);
             v.x = q.x > 0.f ? v.x : 0.f; v.y = q.y > 0.f ? v.y : 0.f; v.z = q.z > 0.f ? v.z : 0.f; v.w = q.w > 0.f ? v.w : 0.f;
           }
-          if (res) v += *reinterpret_cast<const ln_f4*>(res);
-          *reinterpret_cast<ln_f4*>(dst) = v;
+          if (res) v += *reinterpret_cast<const f4*>(res);
+          *reinterpret_cast<f4*>(dst) = v;
         } else {                                                       // rows that are not 16-byte aligned (the corr MLP's 882 columns), the last columns of such a row
 #pragma unroll
           for (int e = 0; e < 4; e++)
@@ -332,7 +293,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 // the request counts are the fp32 kernel's byte for byte).
 // W fp16 (element (n, k) at W[n * s_n + k * s_k]) -> [N / 96][ceil(K / 64)][6 tiles][2 halves of the step][64 lanes][16 B]: lane (n, kg)
 // of tile t, half j holds k = 64 s + 16 kg + 8 j .. + 7 of column 96 nb + 16 t + n (zeros past K).
-__global__ __launch_bounds__(256) void k_pack_weight_f16(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, ln_u4* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_pack_weight_f16(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int N, int K, u4* __restrict__ out) {
   const int nk = (K + 63) / 64;
   const long long total = (long long)(N / LN_BN) * nk * LN_NT * 2 * 64;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
@@ -342,15 +303,12 @@ __global__ __launch_bounds__(256) void k_pack_weight_f16(const __half* __restric
     const int t = (int)(r % LN_NT); r /= LN_NT;
     const int s = (int)(r % nk), nb = (int)(r / nk);
     const int n = nb * LN_BN + 16 * t + (lane & 15), k0 = 64 * s + 16 * (lane >> 4) + 8 * j;
-    ln_h8 v;
-#pragma unroll
-    for (int e = 0; e < 8; e++) v[e] = k0 + e < K ? (_Float16)__half2float(W[(int64_t)n * s_n + (int64_t)(k0 + e) * s_k]) : (_Float16)0.f;
-    out[i] = __builtin_bit_cast(ln_u4, v);
+    out[i] = gather8_f16(reinterpret_cast<const _Float16*>(W), s_n, s_k, n, k0, K);
   }
 }
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_linear_f16(
-    const __half* __restrict__ x, int64_t ldx, const ln_u4* __restrict__ wimg, const __half* __restrict__ bias, const __half* residual,
+    const __half* __restrict__ x, int64_t ldx, const u4* __restrict__ wimg, const __half* __restrict__ bias, const __half* residual,
     __half* y, int64_t ldy, int M, int N, int K, int relu_from) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char ln_lds[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
@@ -360,7 +318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   if (rb * LN_BM >= M) return;
   constexpr unsigned OFF_NONE = 0x80000000u;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(x), 0, (unsigned)(((int64_t)(M - 1) * ldx + K) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<ln_u4*>(wimg), 0, (unsigned)((int64_t)N * nk * 128), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsw = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(wimg), 0, (unsigned)((int64_t)N * nk * 128), 0x00020000);
   const int row_w = rb * LN_BM + LN_MT * 16 * wv;
   unsigned avoff[4];
 #pragma unroll
@@ -384,30 +342,30 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
     for (int q = 0; q < LN_NT * 2 / 4; q++) {
       const int piece = wv + 4 * q;
-      ln_dma16(voff, rsw, (unsigned)(((nb * nk + s) * (LN_NT * 2) + piece) * 1024), lds0 + (unsigned)(buf * LN_STAGE + piece * 1024));
+      lds_dma16(voff, rsw, (unsigned)(((nb * nk + s) * (LN_NT * 2) + piece) * 1024), lds0 + (unsigned)(buf * LN_STAGE + piece * 1024));
     }
   };
   auto load_a = [&](int s) {
 #pragma unroll
     for (int q = 0; q < 4; q++)
-      ln_dma16(s < nk ? avoff[q] : OFF_NONE, rsx, (unsigned)s * 128u, lds0 + (unsigned)(LN_RING + wv * LN_SLAB + q * 1024));
+      lds_dma16(s < nk ? avoff[q] : OFF_NONE, rsx, (unsigned)s * 128u, lds0 + (unsigned)(LN_RING + wv * LN_SLAB + q * 1024));
   };
-  ln_f4 acc[LN_MT][LN_NT];
+  f4 acc[LN_MT][LN_NT];
 #pragma unroll
   for (int mt = 0; mt < LN_MT; mt++)
 #pragma unroll
-    for (int t = 0; t < LN_NT; t++) acc[mt][t] = ln_f4{0.f, 0.f, 0.f, 0.f};
+    for (int t = 0; t < LN_NT; t++) acc[mt][t] = f4{0.f, 0.f, 0.f, 0.f};
   load_a(0);
   stage(0);
   stage(1);
   asm volatile("s_waitcnt vmcnt(3)" ::: "memory");
   __syncthreads();
   for (int s = 0; s < nk; s++) {
-    ln_h8 a[LN_MT][2];
+    h8 a[LN_MT][2];
 #pragma unroll
     for (int mt = 0; mt < LN_MT; mt++)
 #pragma unroll
-      for (int h = 0; h < 2; h++) a[mt][h] = __builtin_bit_cast(ln_h8, *reinterpret_cast<const ln_u4*>(slab + aslot[mt][h]));
+      for (int h = 0; h < 2; h++) a[mt][h] = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(slab + aslot[mt][h]));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     load_a(s + 1);
     stage(s + 2);
@@ -419,14 +377,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
 #pragma unroll
           for (int e = 0; e < 8; e++) a[mt][h][e] = 64 * s + 16 * kg + 8 * h + e < K ? a[mt][h][e] : (_Float16)0.f;
     }
-    const ln_u4* sb = reinterpret_cast<const ln_u4*>(ln_lds + (s % LN_NSTAGE) * LN_STAGE) + lane;
+    const u4* sb = reinterpret_cast<const u4*>(ln_lds + (s % LN_NSTAGE) * LN_STAGE) + lane;
 #pragma unroll
     for (int tg = 0; tg < LN_NT; tg += 3) {
-      ln_h8 b0[3], b1[3];
+      h8 b0[3], b1[3];
 #pragma unroll
       for (int u = 0; u < 3; u++) {
-        b0[u] = __builtin_bit_cast(ln_h8, sb[((tg + u) * 2 + 0) * 64]);
-        b1[u] = __builtin_bit_cast(ln_h8, sb[((tg + u) * 2 + 1) * 64]);
+        b0[u] = __builtin_bit_cast(h8, sb[((tg + u) * 2 + 0) * 64]);
+        b1[u] = __builtin_bit_cast(h8, sb[((tg + u) * 2 + 1) * 64]);
       }
 #pragma unroll
       for (int u = 0; u < 3; u++)
@@ -452,13 +410,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
     for (int t = 0; t < LN_NT; t++)
 #pragma unroll
       for (int r = 0; r < 4; r++) tile[(4 * kg + r) * LN_EPI_LD + 16 * t + mi] = acc[mt][t][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
 #pragma unroll
     for (int it = 0; it < 16 * PPR / 64; it++) {
       const int idx = it * 64 + lane, r = idx / PPR, c4 = idx - r * PPR;
-      ln_f4 v = *reinterpret_cast<const ln_f4*>(tile + r * LN_EPI_LD + 4 * c4) + *reinterpret_cast<const ln_f4*>(colf + 4 * c4);
+      f4 v = *reinterpret_cast<const f4*>(tile + r * LN_EPI_LD + 4 * c4) + *reinterpret_cast<const f4*>(colf + 4 * c4);
       if (col0 + 4 * c4 >= relu_from) { v.x = fmaxf(v.x, 0.f); v.y = fmaxf(v.y, 0.f); v.z = fmaxf(v.z, 0.f); v.w = fmaxf(v.w, 0.f); }
       const int row = row_w + 16 * mt + r;
       if (row < M) {
@@ -497,7 +453,7 @@ int devo_upd_split_weight(const float* W, int64_t s_n, int64_t s_k, int N, int K
   const int nk = (K + 31) / 32, Np = (N + LN_BN - 1) / LN_BN * LN_BN;
   const long long total = (long long)(Np / LN_BN) * nk * LN_NT * 64;
   hipLaunchKernelGGL(k_weight_scales, dim3((unsigned)((Np + 3) / 4)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, Np, N, K, reinterpret_cast<float*>(wsplit) + (size_t)Np * nk * 32);
-  hipLaunchKernelGGL(k_split_weight, dim3((unsigned)blocks_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, Np, N, K, (ln_u4*)wsplit);
+  hipLaunchKernelGGL(k_split_weight, dim3((unsigned)blocks_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, W, s_n, s_k, Np, N, K, (u4*)wsplit);
   return check_launch("devo_upd_split_weight");
 }
 
@@ -513,7 +469,7 @@ int devo_upd_linear_split(const float* x, int64_t ldx, const void* wsplit, const
   static_assert(LN_LDS <= 64 * 1024, "the workgroup's LDS fits the default dynamic limit");
   const int RB = (M + LN_BM - 1) / LN_BM;
   hipLaunchKernelGGL(k_linear_split, dim3((unsigned)(((RB + 7) / 8) * 8 * NB)), dim3(256), LN_LDS, (hipStream_t)stream, x, ldx,
-                     (const ln_u4*)wsplit, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
+                     (const u4*)wsplit, bias, residual, gate, y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
   return check_launch("devo_upd_linear_split");
 }
 
@@ -526,7 +482,7 @@ int devo_upd_pack_weight_f16(const void* W, int64_t s_n, int64_t s_k, int N, int
   DEVO_REQUIRE(N > 0 && K > 0 && N % LN_BN == 0, "devo_upd_pack_weight_f16: N must be a multiple of 96 (got %d x %d)", N, K);
   DEVO_REQUIRE(W && wimage && (reinterpret_cast<uintptr_t>(wimage) & 15) == 0, "devo_upd_pack_weight_f16: null / unaligned tensor");
   const long long total = (long long)(N / LN_BN) * ((K + 63) / 64) * LN_NT * 2 * 64;
-  hipLaunchKernelGGL(k_pack_weight_f16, dim3((unsigned)blocks_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const __half*)W, s_n, s_k, N, K, (ln_u4*)wimage);
+  hipLaunchKernelGGL(k_pack_weight_f16, dim3((unsigned)blocks_for(total, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const __half*)W, s_n, s_k, N, K, (u4*)wimage);
   return check_launch("devo_upd_pack_weight_f16");
 }
 
@@ -540,7 +496,7 @@ int devo_upd_linear_f16(const void* x, int64_t ldx, const void* wimage, const vo
   const int nk = (K + 63) / 64;
   DEVO_REQUIRE(((int64_t)(M - 1) * ldx + K) * 2 < (1LL << 31) && (int64_t)N * nk * 128 < (1LL << 31), "devo_upd_linear_f16: operand beyond 2 GB");
   const int RB = (M + LN_BM - 1) / LN_BM, NB = N / LN_BN;
-  hipLaunchKernelGGL(k_linear_f16, dim3((unsigned)(((RB + 7) / 8) * 8 * NB)), dim3(256), LN_LDS, (hipStream_t)stream, (const __half*)x, ldx, (const ln_u4*)wimage,
+  hipLaunchKernelGGL(k_linear_f16, dim3((unsigned)(((RB + 7) / 8) * 8 * NB)), dim3(256), LN_LDS, (hipStream_t)stream, (const __half*)x, ldx, (const u4*)wimage,
                      (const __half*)bias, (const __half*)residual, (__half*)y, ldy, M, N, K, relu_from < 0 ? 0 : relu_from);
   return check_launch("devo_upd_linear_f16");
 }

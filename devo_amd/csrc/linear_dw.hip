@@ -12,14 +12,11 @@
 // Workgroup = a 128 x 128 block of dW (4 waves x 64 x 64) over a slice of the rows; the slices' partial blocks go to a workspace and a
 // second kernel adds them up (no atomics: the result is reproducible).
 #include "common.h"
+#include "f16split.h"
 #include <hip/hip_fp16.h>
 #include <algorithm>
 
 namespace devo {
-
-typedef _Float16 dw_h8 __attribute__((ext_vector_type(8)));
-typedef float dw_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned dw_u4 __attribute__((ext_vector_type(4)));
 
 constexpr int DW_BT = 128;                        // block of dW per workgroup: 128 columns of dY x 128 columns of X
 constexpr int DW_ROWS = 32;                       // rows per step (the MFMA's K)
@@ -27,31 +24,6 @@ constexpr int DW_INSTR = 1024 + 16;               // LDS bytes of one DMA instru
 constexpr int DW_TILE = 16 * DW_INSTR;            // one operand tile of a stage
 constexpr int DW_STAGE = 2 * DW_TILE;
 constexpr int DW_LDS = 2 * DW_STAGE;              // two stages: 66 560 B, two workgroups per CU
-constexpr int DW_EXP_TARGET = 8;
-constexpr float DW_RAISE = 16384.f;
-
-__device__ __forceinline__ void dw_split8(const float (&x)[8], dw_h8& hi, dw_h8& lo) {
-  unsigned h[4], l[4];
-#pragma unroll
-  for (int j = 0; j < 4; j++) {
-    asm("v_cvt_pk_f16_f32 %0, %1, %2" : "=v"(h[j]) : "v"(x[2 * j]), "v"(x[2 * j + 1]));
-    asm("v_fma_mixlo_f16 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(l[j]) : "v"(h[j]), "v"(x[2 * j]));
-    asm("v_fma_mixhi_f16 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(l[j]) : "v"(h[j]), "v"(x[2 * j + 1]));
-  }
-  const dw_u4 hv = {h[0], h[1], h[2], h[3]}, lv = {l[0], l[1], l[2], l[3]};
-  hi = __builtin_bit_cast(dw_h8, hv);
-  lo = __builtin_bit_cast(dw_h8, lv);
-}
-__device__ __forceinline__ int dw_scale_exp(float m) {
-  int e = (int)((__float_as_uint(m) >> 23) & 255u);
-  e = e < 16 ? 16 : e;
-  return 127 + DW_EXP_TARGET + 127 - e;
-}
-__device__ __forceinline__ float dw_pow2(int biased) { return __uint_as_float((unsigned)(biased < 0 ? 0 : (biased > 254 ? 254 : biased)) << 23); }
-__device__ __forceinline__ void dw_dma16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned lds_addr) {
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, 0 offen lds" ::"v"(voff), "s"(rs), "s"(lds_addr) : "memory");
-}
 
 // grid = (blocks of dW) x splits.  part [splits][No][Ni], gpart [splits][No] (the bias gradient's partial sums, written by the workgroups of
 // the first block column).
@@ -86,8 +58,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     const unsigned go = (unsigned)s * gstep, xo = (unsigned)s * xstep;
 #pragma unroll
     for (int q = 0; q < 4; q++) {
-      dw_dma16(any && gvoff[q] != OFF_NONE ? gvoff[q] + go : OFF_NONE, rg, lds0 + (unsigned)(buf * DW_STAGE + (wv + 4 * q) * DW_INSTR));
-      dw_dma16(any && xvoff[q] != OFF_NONE ? xvoff[q] + xo : OFF_NONE, rx, lds0 + (unsigned)(buf * DW_STAGE + DW_TILE + (wv + 4 * q) * DW_INSTR));
+      lds_dma16(any && gvoff[q] != OFF_NONE ? gvoff[q] + go : OFF_NONE, rg, lds0 + (unsigned)(buf * DW_STAGE + (wv + 4 * q) * DW_INSTR));
+      lds_dma16(any && xvoff[q] != OFF_NONE ? xvoff[q] + xo : OFF_NONE, rx, lds0 + (unsigned)(buf * DW_STAGE + DW_TILE + (wv + 4 * q) * DW_INSTR));
     }
   };
   // operand reads: lane (column li of tile t, row group kg) -> rows 8 kg + q, q = 0 .. 7: four ds_read2_b32 (rows 2 u, 2 u + 1)
@@ -102,11 +74,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     }
   };
 
-  dw_f4 acc[4][4];
+  f4 acc[4][4];
 #pragma unroll
   for (int a = 0; a < 4; a++)
 #pragma unroll
-    for (int b = 0; b < 4; b++) acc[a][b] = dw_f4{0.f, 0.f, 0.f, 0.f};
+    for (int b = 0; b < 4; b++) acc[a][b] = f4{0.f, 0.f, 0.f, 0.f};
   float scA[4], scB[4], gsum[4];
   int eA[4], eB[4];
 #pragma unroll
@@ -145,7 +117,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       n = fmaxf(fmaxf(n, fabsf(xb[t][3])), fabsf(xb[t][4]));
       n = fmaxf(fmaxf(n, fabsf(xb[t][5])), fmaxf(fabsf(xb[t][6]), fabsf(xb[t][7])));
       mb[t] = n;
-      raise = raise || !(m * scA[t] <= DW_RAISE) || !(n * scB[t] <= DW_RAISE);
+      raise = raise || !(m * scA[t] <= F16_SPLIT_RAISE) || !(n * scB[t] <= F16_SPLIT_RAISE);
       if (do_bias) gsum[t] += ((xa[t][0] + xa[t][1]) + (xa[t][2] + xa[t][3])) + ((xa[t][4] + xa[t][5]) + (xa[t][6] + xa[t][7]));
     }
     const bool first = s == s_begin;
@@ -156,22 +128,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         float m = ma[t];
         m = fmaxf(m, __shfl_xor(m, 16));
         m = fmaxf(m, __shfl_xor(m, 32));
-        const bool need = first || !(m * scA[t] <= DW_RAISE);
-        const int en = need ? dw_scale_exp(m) : eA[t];
-        fa[t] = first ? 1.f : dw_pow2(127 + en - eA[t]);
-        eA[t] = en; scA[t] = dw_pow2(en);
+        const bool need = first || !(m * scA[t] <= F16_SPLIT_RAISE);
+        const int en = need ? scale_exp(m) : eA[t];
+        fa[t] = first ? 1.f : pow2_biased(127 + en - eA[t]);
+        eA[t] = en; scA[t] = pow2_biased(en);
         float n = mb[t];
         n = fmaxf(n, __shfl_xor(n, 16));
         n = fmaxf(n, __shfl_xor(n, 32));
-        const bool needb = first || !(n * scB[t] <= DW_RAISE);
-        const int enb = needb ? dw_scale_exp(n) : eB[t];
-        fb[t] = first ? 1.f : dw_pow2(127 + enb - eB[t]);
-        eB[t] = enb; scB[t] = dw_pow2(enb);
+        const bool needb = first || !(n * scB[t] <= F16_SPLIT_RAISE);
+        const int enb = needb ? scale_exp(n) : eB[t];
+        fb[t] = first ? 1.f : pow2_biased(127 + enb - eB[t]);
+        eB[t] = enb; scB[t] = pow2_biased(enb);
       }
       if (!first) {
 #pragma unroll
         for (int a = 0; a < 4; a++) {
-          dw_f4 fr;                                                     // D rows 4 kg + r of tile a = columns 4 kg + r of the dY tile
+          f4 fr;                                                     // D rows 4 kg + r of tile a = columns 4 kg + r of the dY tile
 #pragma unroll
           for (int r = 0; r < 4; r++) fr[r] = __shfl(fa[a], 4 * kg + r);
 #pragma unroll
@@ -179,13 +151,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         }
       }
     }
-    dw_h8 ah[4], al[4], bh[4], bl[4];
+    h8 ah[4], al[4], bh[4], bl[4];
 #pragma unroll
     for (int t = 0; t < 4; t++) {
 #pragma unroll
       for (int j = 0; j < 8; j++) { xa[t][j] *= scA[t]; xb[t][j] *= scB[t]; }
-      dw_split8(xa[t], ah[t], al[t]);
-      dw_split8(xb[t], bh[t], bl[t]);
+      split8(xa[t], ah[t], al[t]);
+      split8(xb[t], bh[t], bl[t]);
     }
 #pragma unroll
     for (int a = 0; a < 4; a++)                                        // small terms first; the same accumulator again 16 MFMAs later
@@ -207,13 +179,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   float* pb = part + ((size_t)sp * Nop + i0 + 64 * wi) * Nip + j0 + 64 * wj;
 #pragma unroll
   for (int a = 0; a < 4; a++) {
-    const float ia = dw_pow2(254 - eA[a]);
-    dw_f4 ir;
+    const float ia = pow2_biased(254 - eA[a]);
+    f4 ir;
 #pragma unroll
     for (int r = 0; r < 4; r++) ir[r] = __shfl(ia, 4 * kg + r);
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-      const float ib = dw_pow2(254 - eB[b]);
+      const float ib = pow2_biased(254 - eB[b]);
 #pragma unroll
       for (int r = 0; r < 4; r++) pb[(size_t)(16 * a + 4 * kg + r) * Nip + 16 * b + li] = acc[a][b][r] * ir[r] * ib;
     }
@@ -237,10 +209,10 @@ __global__ __launch_bounds__(256) void k_dw_reduce(const float* __restrict__ par
   if (i < n4) {
     const int row = i / q4, col = 4 * (i - row * q4);
     if (col >= Ni) return;
-    dw_f4 t = {0.f, 0.f, 0.f, 0.f};
-    for (int s = 0; s < splits; s++) t += *reinterpret_cast<const dw_f4*>(part + ((size_t)s * Nop + row) * Nip + col);
+    f4 t = {0.f, 0.f, 0.f, 0.f};
+    for (int s = 0; s < splits; s++) t += *reinterpret_cast<const f4*>(part + ((size_t)s * Nop + row) * Nip + col);
     float* dst = dW + (size_t)row * ld_dw + col;
-    if (col + 4 <= Ni && (ld_dw & 3) == 0 && (reinterpret_cast<uintptr_t>(dW) & 15) == 0) *reinterpret_cast<dw_f4*>(dst) = t;
+    if (col + 4 <= Ni && (ld_dw & 3) == 0 && (reinterpret_cast<uintptr_t>(dW) & 15) == 0) *reinterpret_cast<f4*>(dst) = t;
     else
       for (int e = 0; e < 4; e++) if (col + e < Ni) dst[e] = t[e];
   } else if (db && i - n4 < No) {

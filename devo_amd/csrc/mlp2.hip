@@ -14,13 +14,10 @@
 // leaves through the idle weight ring as whole 16-byte pieces, with the bias and the optional residual.
 // 152 KB of LDS: one workgroup (two waves per SIMD) per CU; 21 600 rows = 169 workgroups.
 #include "common.h"
+#include "f16split.h"
 #include <hip/hip_fp16.h>
 
 namespace devo {
-
-typedef _Float16 mp_h8 __attribute__((ext_vector_type(8)));
-typedef float mp_f4 __attribute__((ext_vector_type(4)));
-typedef unsigned mp_u4 __attribute__((ext_vector_type(4)));
 
 constexpr int MP_N = 384;                          // width of both layers' outputs
 constexpr int MP_T = MP_N / 16;                    // column tiles
@@ -34,43 +31,28 @@ constexpr int MP_LDS = MP_NSTW * MP_STAGE + 8 * MP_NST * MP_SLAB + 8 * 1024 + 2 
 
 // W fp16, element (n, k) at W[n * s_n + k * s_k], n < 384 -> [ceil(K / 32)][24 tiles][64 lanes][16 B]: lane (n, kg) of tile t and step s holds
 // k = 32 s + 8 kg .. + 7 of column 16 t + n (zeros past K)
-__global__ __launch_bounds__(256) void k_mlp2_pack(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int K, mp_u4* __restrict__ out) {
+__global__ __launch_bounds__(256) void k_mlp2_pack(const __half* __restrict__ W, int64_t s_n, int64_t s_k, int K, u4* __restrict__ out) {
   const int nk = (K + 31) / 32;
   const int total = nk * MP_T * 64;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < total; i += gridDim.x * 256) {
     const int lane = i & 63, t = (i >> 6) % MP_T, s = (i >> 6) / MP_T;
     const int n = 16 * t + (lane & 15), k0 = 32 * s + 8 * (lane >> 4);
-    mp_h8 v;
-#pragma unroll
-    for (int e = 0; e < 8; e++) v[e] = k0 + e < K ? (_Float16)__half2float(W[(int64_t)n * s_n + (int64_t)(k0 + e) * s_k]) : (_Float16)0.f;
-    out[i] = __builtin_bit_cast(mp_u4, v);
+    out[i] = gather8_f16(reinterpret_cast<const _Float16*>(W), s_n, s_k, n, k0, K);
   }
-}
-
-__device__ __forceinline__ void mp_dma16(unsigned voff, __amdgpu_buffer_rsrc_t rs, unsigned soff, unsigned lds_addr) {
-  lds_addr = (unsigned)__builtin_amdgcn_readfirstlane((int)lds_addr);
-  soff = (unsigned)__builtin_amdgcn_readfirstlane((int)soff);
-  asm volatile("s_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %0, %1, %3 offen lds" ::"v"(voff), "s"(rs), "s"(lds_addr), "s"(soff) : "memory");
-}
-
-__device__ __forceinline__ void mp_wave_lds_fence() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 template <bool GATHER>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) void k_mlp2_f16(
-    const __half* __restrict__ x, int64_t ldx, int x_rows, const int64_t* __restrict__ gather, const mp_u4* __restrict__ w1, const __half* __restrict__ b1,
-    int K1, const mp_u4* __restrict__ w2, const __half* __restrict__ b2, const __half* residual, __half* y, int64_t ldy, int M) {
+    const __half* __restrict__ x, int64_t ldx, int x_rows, const int64_t* __restrict__ gather, const u4* __restrict__ w1, const __half* __restrict__ b1,
+    int K1, const u4* __restrict__ w2, const __half* __restrict__ b2, const __half* residual, __half* y, int64_t ldy, int M) {
   extern __shared__ __attribute__((aligned(1024))) unsigned char mp_lds[];
   const int tid = threadIdx.x, wv = __builtin_amdgcn_readfirstlane(tid >> 6), lane = tid & 63, mi = lane & 15, kg = lane >> 4;
   const int row0 = blockIdx.x * MP_ROWS + 16 * wv;                    // this wave's 16 rows (all 384 columns of them)
   const int nk1 = (K1 + 31) / 32, nst = nk1 + MP_NK;
   constexpr unsigned OFF_NONE = 0x80000000u;
   const __amdgpu_buffer_rsrc_t rsx = __builtin_amdgcn_make_buffer_rsrc(const_cast<__half*>(x), 0, (unsigned)(((int64_t)(x_rows - 1) * ldx + K1) * 2), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<mp_u4*>(w1), 0, (unsigned)(nk1 * MP_STAGE), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<mp_u4*>(w2), 0, (unsigned)(MP_NK * MP_STAGE), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(w1), 0, (unsigned)(nk1 * MP_STAGE), 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs2 = __builtin_amdgcn_make_buffer_rsrc(const_cast<u4*>(w2), 0, (unsigned)(MP_NK * MP_STAGE), 0x00020000);
   const unsigned lds0 = (unsigned)(uintptr_t)mp_lds;
   // layer 1's rows: lane L requests piece L & 3 (16 bytes) of row L >> 2 — a quad of lanes = the 64 contiguous bytes of a row's K step —
   // into slot L of the wave's slab; lane (mi, kg) then reads slot 4 mi + kg
@@ -95,15 +77,15 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       const int piece = wv + 8 * q;
       const unsigned voff = g < nst ? (unsigned)lane * 16u : OFF_NONE;
       const bool first = g < nk1;
-      mp_dma16(voff, first ? rs1 : rs2, (unsigned)(((first ? g : g - nk1) * MP_T + piece) * 1024), lds0 + (unsigned)(buf * MP_STAGE + piece * 1024));
+      lds_dma16(voff, first ? rs1 : rs2, (unsigned)(((first ? g : g - nk1) * MP_T + piece) * 1024), lds0 + (unsigned)(buf * MP_STAGE + piece * 1024));
     }
   };
   auto load_a = [&](int s) {                                          // K step s of this wave's rows -> slab s % 3 (behind the last step: zeros, no access)
-    mp_dma16(s < nk1 ? arow : OFF_NONE, rsx, (unsigned)s * 64u, (unsigned)(uintptr_t)slab + (unsigned)((s % MP_NST) * MP_SLAB));
+    lds_dma16(s < nk1 ? arow : OFF_NONE, rsx, (unsigned)s * 64u, (unsigned)(uintptr_t)slab + (unsigned)((s % MP_NST) * MP_SLAB));
   };
-  mp_f4 acc[MP_T];
+  f4 acc[MP_T];
 #pragma unroll
-  for (int t = 0; t < MP_T; t++) acc[t] = mp_f4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < MP_T; t++) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
   // Request order: rows(0) W(0) rows(1) W(1) W(2) W(3), then per step g: rows(g + 2) W(g + 4).  Every vector-memory request of the loops is an
   // LDS-DMA, 1 per row slab and 3 per weight stage and wave, so the waits are counted by hand: behind step g everything up to rows(g + 1) must
   // be there — W(g + 1) and W(g + 2) are older — which leaves W(g + 3), rows(g + 2), W(g + 4) = 7 requests in flight.
@@ -117,10 +99,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   __syncthreads();
   // a step's 24 products: the weight fragments of six tiles are read while the previous six multiply (left to itself the compiler keeps two
   // fragments in flight and waits for the LDS before every product: 2.6 k cycles per step where the matrix pipe and the LDS need 0.8 k each)
-  auto products = [&](int g, mp_h8 a) {
-    const mp_u4* sb = reinterpret_cast<const mp_u4*>(mp_lds + (g % MP_NSTW) * MP_STAGE) + lane;
+  auto products = [&](int g, h8 a) {
+    const u4* sb = reinterpret_cast<const u4*>(mp_lds + (g % MP_NSTW) * MP_STAGE) + lane;
     constexpr int GB = 6;
-    mp_u4 b[2][GB];
+    u4 b[2][GB];
 #pragma unroll
     for (int u = 0; u < GB; u++) b[0][u] = sb[u * 64];
 #pragma unroll
@@ -131,13 +113,13 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int u = 0; u < GB; u++) acc[k * GB + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(mp_h8, b[k & 1][u]), acc[k * GB + u], 0, 0, 0);
+      for (int u = 0; u < GB; u++) acc[k * GB + u] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, __builtin_bit_cast(h8, b[k & 1][u]), acc[k * GB + u], 0, 0, 0);
       __builtin_amdgcn_sched_barrier(0);
     }
   };
   // ---- layer 1: K steps 0 .. nk1 - 1
   for (int g = 0; g < nk1; g++) {
-    mp_h8 a = __builtin_bit_cast(mp_h8, *reinterpret_cast<const mp_u4*>(slab + (g % MP_NST) * MP_SLAB + (4 * mi + kg) * 16));
+    h8 a = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(slab + (g % MP_NST) * MP_SLAB + (4 * mi + kg) * 16));
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     load_a(g + 2);
     stage(g + 4);
@@ -152,7 +134,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // ---- the intermediate relu(acc + b1), fp16 (rounded like the two-launch form's), from the result layout (lane = column n, rows 4 kg + j) into
   //      the A-operand layout (lane = row mi, 8 consecutive k) through the wave's own KB of LDS, one K step (two column tiles) at a time; it stays
   //      in 48 registers
-  mp_u4 a2[MP_NK];
+  u4 a2[MP_NK];
 #pragma unroll
   for (int s2 = 0; s2 < MP_NK; s2++) {
 #pragma unroll
@@ -163,19 +145,19 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int j = 0; j < 4; j++) *reinterpret_cast<_Float16*>(cell + (4 * kg + j) * 16) = (_Float16)fmaxf(acc[T][j] + bv, 0.f);
     }
-    mp_wave_lds_fence();                                              // (a wave's LDS operations execute in order; this pins the compiler's)
-    a2[s2] = *reinterpret_cast<const mp_u4*>(bounce + lane * 16);
-    mp_wave_lds_fence();
+    wave_lds_handoff();                                               // (a wave's LDS operations execute in order; this pins the compiler's)
+    a2[s2] = *reinterpret_cast<const u4*>(bounce + lane * 16);
+    wave_lds_handoff();
   }
 #pragma unroll
-  for (int t = 0; t < MP_T; t++) acc[t] = mp_f4{0.f, 0.f, 0.f, 0.f};
+  for (int t = 0; t < MP_T; t++) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
   // ---- layer 2: K steps nk1 .. nk1 + 11, the rows from the registers
 #pragma unroll
   for (int s2 = 0; s2 < MP_NK; s2++) {
     const int g = nk1 + s2;
     load_a(g + 2);                                                    // (no rows left: the out-of-range offset — the request count per step stays 4)
     stage(g + 4);
-    products(g, __builtin_bit_cast(mp_h8, a2[s2]));
+    products(g, __builtin_bit_cast(h8, a2[s2]));
     asm volatile("s_waitcnt vmcnt(7)" ::: "memory");
     __syncthreads();
   }
@@ -192,23 +174,23 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 #pragma unroll
       for (int j = 0; j < 4; j++) *reinterpret_cast<_Float16*>(outb + (4 * kg + j) * 400 + (16 * t + mi) * 2) = (_Float16)(acc[T][j] + bv);
     }
-    mp_wave_lds_fence();
+    wave_lds_handoff();
 #pragma unroll
     for (int it = 0; it < 6; it++) {
       const int c = it * 64 + lane, r = c / 24, c8 = c - r * 24;     // row of the wave, group of 8 columns of the half
       const int row = row0 + r;
-      mp_h8 v = __builtin_bit_cast(mp_h8, *reinterpret_cast<const mp_u4*>(outb + r * 400 + c8 * 16));
+      h8 v = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(outb + r * 400 + c8 * 16));
       if (row < M) {
         const int64_t o = (int64_t)row * ldy + 192 * hc + 8 * c8;
         if (residual) {
-          const mp_h8 rr = __builtin_bit_cast(mp_h8, *reinterpret_cast<const mp_u4*>(residual + o));
+          const h8 rr = __builtin_bit_cast(h8, *reinterpret_cast<const u4*>(residual + o));
 #pragma unroll
           for (int e = 0; e < 8; e++) v[e] = (_Float16)((float)v[e] + (float)rr[e]);
         }
-        *reinterpret_cast<mp_u4*>(y + o) = __builtin_bit_cast(mp_u4, v);
+        *reinterpret_cast<u4*>(y + o) = __builtin_bit_cast(u4, v);
       }
     }
-    mp_wave_lds_fence();
+    wave_lds_handoff();
   }
 }
 
@@ -223,7 +205,7 @@ size_t devo_upd_mlp2_weight_bytes(int K) { return K > 0 ? (size_t)((K + 31) / 32
 int devo_upd_mlp2_pack_weight(const void* W, int64_t s_n, int64_t s_k, int K, void* wimage, devo_stream_t stream) {
   DEVO_REQUIRE(K > 0 && W && wimage && (reinterpret_cast<uintptr_t>(wimage) & 15) == 0, "devo_upd_mlp2_pack_weight: bad arguments (K = %d)", K);
   const int total = (K + 31) / 32 * MP_T * 64;
-  hipLaunchKernelGGL(k_mlp2_pack, dim3((unsigned)blocks_for(total, 256, 1024)), dim3(256), 0, (hipStream_t)stream, (const __half*)W, s_n, s_k, K, (mp_u4*)wimage);
+  hipLaunchKernelGGL(k_mlp2_pack, dim3((unsigned)blocks_for(total, 256, 1024)), dim3(256), 0, (hipStream_t)stream, (const __half*)W, s_n, s_k, K, (u4*)wimage);
   return check_launch("devo_upd_mlp2_pack_weight");
 }
 
@@ -244,11 +226,11 @@ int devo_upd_mlp2_f16(const void* x, int64_t ldx, int x_rows, const int64_t* gat
   }
   const dim3 grid((unsigned)((M + MP_ROWS - 1) / MP_ROWS)), block(512);
   if (gather)
-    hipLaunchKernelGGL(k_mlp2_f16<true>, grid, block, MP_LDS, (hipStream_t)stream, (const __half*)x, ldx, x_rows, gather, (const mp_u4*)w1image, (const __half*)b1, K1,
-                       (const mp_u4*)w2image, (const __half*)b2, (const __half*)residual, (__half*)y, ldy, M);
+    hipLaunchKernelGGL(k_mlp2_f16<true>, grid, block, MP_LDS, (hipStream_t)stream, (const __half*)x, ldx, x_rows, gather, (const u4*)w1image, (const __half*)b1, K1,
+                       (const u4*)w2image, (const __half*)b2, (const __half*)residual, (__half*)y, ldy, M);
   else
-    hipLaunchKernelGGL(k_mlp2_f16<false>, grid, block, MP_LDS, (hipStream_t)stream, (const __half*)x, ldx, x_rows, gather, (const mp_u4*)w1image, (const __half*)b1, K1,
-                       (const mp_u4*)w2image, (const __half*)b2, (const __half*)residual, (__half*)y, ldy, M);
+    hipLaunchKernelGGL(k_mlp2_f16<false>, grid, block, MP_LDS, (hipStream_t)stream, (const __half*)x, ldx, x_rows, gather, (const u4*)w1image, (const __half*)b1, K1,
+                       (const u4*)w2image, (const __half*)b2, (const __half*)residual, (__half*)y, ldy, M);
   return check_launch("devo_upd_mlp2_f16");
 }
 

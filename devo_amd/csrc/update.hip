@@ -11,6 +11,7 @@
 // All kernels: fp32 or fp16 storage (DEVO runs the update under autocast), fp32 arithmetic, one wave per row where a
 // row reduction is needed (dim = 384 -> 6 elements per lane), no atomics, fixed summation order.
 #include "common.h"
+#include "f16split.h"
 #include <hip/hip_fp16.h>
 #include <initializer_list>
 
@@ -353,17 +354,8 @@ __global__ __launch_bounds__(256) void k_layernorm_v(const T* __restrict__ x, co
   }
 }
 
-// Sum over the 16 lanes of a DPP row, result in all of them (row_ror 8, 4, 2, 1): no LDS round trips.
-__device__ __forceinline__ float row16_sum(float v) {
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x128, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x124, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x122, 0xf, 0xf, false));
-  v += __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), 0x121, 0xf, 0xf, false));
-  return v;
-}
-
 // k_layernorm with a QUARTER wave per row (16 lanes x NC 16-byte chunks, cpr = 16 NC <= 128): four rows per wave, the two row
-// reductions inside a DPP row.  A whole wave per 768-byte row spends its time in two 6-step shuffle chains.
+// reductions inside a DPP row (row16_sum, f16split.h).  A whole wave per 768-byte row spends its time in two 6-step shuffle chains.
 template <typename T, int NC>
 __global__ __launch_bounds__(256) void k_layernorm_q(const T* __restrict__ x, const T* __restrict__ a, const T* __restrict__ b,
                                                      const T* __restrict__ hy, const int* __restrict__ group_of,
