@@ -159,7 +159,8 @@ __global__ __launch_bounds__(64 * MFMA_EPW) __attribute__((amdgpu_waves_per_eu(M
     // — no passes at all for this level, the epilogue writes zeros
     if (xmax + D <= 0 || ymax + D <= 0 || xmin >= LVF(l, W2) || ymin >= LVF(l, H2)) { g.nslots = 0; g.box_mode = true; }
     g.npass = (g.nslots + 63) >> 6;
-    g.boxlay = g.box_mode && g.nslots <= BOXS;
+    // (a level without passes takes the D x D layout: its epilogue reads windows at the area's start, whatever the box's width)
+    g.boxlay = g.box_mode && g.nslots > 0 && g.nslots <= BOXS;
     g.inv_bw = __builtin_amdgcn_rcpf((float)g.bw);       // 1 ulp is plenty for the row / column split below
     return g;
   };
