@@ -686,6 +686,14 @@ void pg_append(Tensor ii, Tensor jj, Tensor kk, Tensor net_old, Tensor net_new, 
                           i64p(frame_ids), (int)E, (int)n_new, (int)ii.numel(), (int)net_new.size(-1), dtype_code(net_new), stream_of(ii)), "patch_graph.append");
 }
 
+void pg_append_frame(Tensor ii, Tensor jj, Tensor kk, Tensor net_old, Tensor net_new, Tensor ix, int64_t M, int64_t n, int64_t lifetime, int64_t E) {
+  for (const Tensor* t : {&ii, &jj, &kk, &ix}) pg_check_idx("patch_graph.append_frame", *t);
+  require_gpu(net_old, net_new);
+  c10::DeviceGuard guard(ii.device());
+  check(devo_odom_append_frame(ii.data_ptr<int64_t>(), jj.data_ptr<int64_t>(), kk.data_ptr<int64_t>(), net_old.data_ptr(), net_new.data_ptr(), i64p(ix), ix.numel(), (int)M,
+                               (int)n, (int)lifetime, (int)E, (int)ii.numel(), (int)net_new.size(-1), dtype_code(net_new), stream_of(ii)), "patch_graph.append_frame");
+}
+
 void pg_shift_frames(TensorList tensors, int64_t k, int64_t n) {
   if (tensors.empty()) return;
   std::vector<void*> ptrs;
@@ -1103,6 +1111,31 @@ void fr_complete(Tensor poses, Tensor tstamps, int64_t n, int64_t counter, Tenso
                             ws.data_ptr(), (size_t)(ws.numel() * ws.element_size()), status.data_ptr<int>(), stream_of(parent)), "frames.complete");
 }
 
+// devo_odom_input / devo_odom_probe_median (csrc/frame_input.hip).  `record` (4 doubles) and the median's `out` may be pinned HOST tensors.
+void fr_check_host_visible(const char* what, const Tensor& t, at::ScalarType dt, int64_t n) {
+  TORCH_CHECK((t.is_cuda() || t.is_pinned()) && t.scalar_type() == dt && t.is_contiguous() && t.numel() >= n, what, ": expected a contiguous GPU or pinned host tensor of at least ", n,
+              " elements");
+}
+
+void fr_input(Tensor vox, int64_t norm, Tensor out, Tensor ws, Tensor record) {
+  require_gpu(vox, out, ws);
+  TORCH_CHECK(vox.dim() == 3 && vox.is_contiguous() && (vox.scalar_type() == at::kFloat || vox.scalar_type() == at::kHalf), "frames.frame_input: the voxel grid must be a contiguous fp32 or fp16 [bins, H, W] tensor");
+  const int64_t W = vox.size(2), Wout = W == DEVO_INPUT_CROP_WIDTH ? W - 2 : W;
+  TORCH_CHECK(out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() == vox.size(0) * vox.size(1) * Wout, "frames.frame_input: out must be a contiguous float32 tensor of bins x H x ", Wout, " elements");
+  fr_check_host_visible("frames.frame_input (record)", record, at::kDouble, 4);
+  c10::DeviceGuard guard(vox.device());
+  check(devo_odom_input(vox.data_ptr(), dtype_code(vox), (int)vox.size(0), (int)vox.size(1), (int)W, (int)norm, out.data_ptr<float>(), ws.data_ptr(), (size_t)ws.numel(),
+                        record.data_ptr<double>(), stream_of(vox)), "frames.frame_input");
+}
+
+void fr_probe_median(Tensor delta, Tensor out) {
+  require_gpu(delta);
+  TORCH_CHECK(delta.is_contiguous() && delta.numel() % 2 == 0 && (delta.scalar_type() == at::kFloat || delta.scalar_type() == at::kHalf), "frames.probe_median: delta must be a contiguous fp32 or fp16 [1, M, 2] tensor");
+  fr_check_host_visible("frames.probe_median (out)", out, at::kFloat, 1);
+  c10::DeviceGuard guard(delta.device());
+  check(devo_odom_probe_median(delta.data_ptr(), dtype_code(delta), (int)(delta.numel() / 2), out.data_ptr<float>(), stream_of(delta)), "frames.probe_median");
+}
+
 // ------------------------------------------------------------------------------------------------ training loss (devo_amd/losses.py; csrc/loss.hip)
 // Thin forms of devo_loss_forward / devo_loss_backward: the outputs and the state are allocated here, nothing else happens on the host.
 void loss_check(const char* what, const Tensor& t, at::ScalarType dt) {
@@ -1302,6 +1335,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   pg.def("keyframe", &pg_keyframe);
   pg.def("remove", &pg_remove);
   pg.def("append", &pg_append);
+  pg.def("append_frame", &pg_append_frame);
+  pg.def("append_frame_edges", [](int64_t M, int64_t n, int64_t lifetime) { return (int64_t)devo_odom_append_frame_edges((int)M, (int)n, (int)lifetime); });
   pg.def("shift_frames", &pg_shift_frames);
   pg.def("workspace_bytes", [](int64_t capacity) { return (int64_t)devo_graph_workspace_bytes((int)capacity); });
   auto tg = m.def_submodule("train_graph", "devo_amd.train_graph: devo/enet.py:297-339, :359-369 on the graph");
@@ -1345,6 +1380,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   fr.def("complete", &fr_complete);
   fr.def("complete_workspace_bytes", [](int64_t counter) { return (int64_t)devo_frame_complete_workspace_bytes((int)counter); });
   fr.def("complete_launches", [](int64_t counter) { return (int64_t)devo_frame_complete_launches((int)counter); });
+  fr.def("frame_input", &fr_input);
+  fr.def("frame_input_workspace_bytes", [](int64_t numel) { return (int64_t)devo_odom_input_workspace_bytes(numel); });
+  fr.def("probe_median", &fr_probe_median);
   auto losses = m.def_submodule("losses", "devo_amd.losses: train.py:172-236, :254-266");
   losses.def("forward", &loss_forward);
   losses.def("backward", &loss_backward);

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <cmath>
 #include "common.h"
+#include "voxel_sigma.h"
 
 namespace devo {
 
@@ -84,7 +85,7 @@ __global__ void k_voxel_normalise(float* __restrict__ v, int64_t len, int nseg, 
   const int seg = blockIdx.y;
   const double cnt = stats[3 * seg];
   const float mean = (float)(stats[3 * seg + 1] / cnt);
-  const float sd = sqrtf((float)(stats[3 * seg + 2] / cnt) - mean * mean);
+  const float sd = voxel_sigma_f32((float)(stats[3 * seg + 2] / cnt), mean);                     // (the fused multiply-add this line always compiled to)
   float* p = v + (int64_t)seg * len;
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < len; i += (int64_t)gridDim.x * blockDim.x) {
     const float a = p[i];

@@ -11,6 +11,8 @@
 //     64-bit ballot + popcount, per-workgroup offsets from the sum of the workgroup counts in front; rows of net move as 16-byte words.
 //     The last workgroup writes {removed, n_edges, mean_ij, mean_ji} into a host-visible record: the caller waits once, for that.
 //   * k_append: index tails written in place (ii = ix[patch_ids] gathered here) and the new net (old rows copied, new rows zero).
+//   * k_append_frame: the same for the window edges of a new frame (devo.py:366-380, :541-542), whose patch and frame ids are computed
+//     from (M, n, lifetime) instead of read: both append_factors calls of a frame in one launch, no index lists built on the host.
 //   * k_shift_frames: rows k+1 .. n-1 of up to 8 tensors, addressed as byte rows, move down by one.  A thread owns a column chunk and
 //     walks the rows in ascending order: it has read row r + 1 before it overwrites it, and nobody else touches its columns.
 // Nothing here synchronises with the host.
@@ -242,6 +244,32 @@ __global__ __launch_bounds__(TB) void k_append(int64_t* __restrict__ ii, int64_t
   for (int64_t t = t0; t < n_all; t += stride) net_new[t] = t < n_old ? net_old[t] : zero;
 }
 
+// the window edges of frame n - 1 (devo.py:366-380, :541-542), generated here instead of read from index lists: n_fwd forward edges
+// (patch p0 + t -> frame n - 1), then the backward edges of the newest M patches, patch-major over the frames f0 .. n - 1
+struct FrameEdges { int n_fwd, n_new, p0, pb0, f0, nf, last; };
+
+inline FrameEdges frame_edges(int M, int n, int lifetime) {
+  const int f0 = std::max(n - lifetime, 0), nf = n - f0;
+  const long long n_fwd = (long long)M * (n - 1 - std::min(f0, n - 1)), n_new = n_fwd + (long long)M * nf;
+  return FrameEdges{(int)n_fwd, (int)n_new, M * std::min(f0, n - 1), M * (n - 1), f0, nf, n - 1};
+}
+
+__global__ __launch_bounds__(TB) void k_append_frame(int64_t* __restrict__ ii, int64_t* __restrict__ jj, int64_t* __restrict__ kk, const uint4* __restrict__ net_old,
+                                                     uint4* __restrict__ net_new, const int64_t* __restrict__ ix, int64_t ix_len, FrameEdges e, int E, int cpr) {
+  const int64_t stride = (int64_t)gridDim.x * TB, t0 = (int64_t)blockIdx.x * TB + threadIdx.x;
+  for (int64_t t = t0; t < e.n_new; t += stride) {
+    int64_t p, f;
+    if (t < e.n_fwd) { p = e.p0 + t; f = e.last; }
+    else { const int64_t b = t - e.n_fwd, q = b / e.nf; p = e.pb0 + q; f = e.f0 + (b - q * e.nf); }
+    kk[E + t] = p;
+    jj[E + t] = f;
+    ii[E + t] = p < ix_len ? ix[p] : -1;
+  }
+  const int64_t n_old = (int64_t)E * cpr, n_all = ((int64_t)E + e.n_new) * cpr;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (int64_t t = t0; t < n_all; t += stride) net_new[t] = t < n_old ? net_old[t] : zero;
+}
+
 constexpr int SHIFT_MAX = DEVO_GRAPH_SHIFT_MAX;
 struct ShiftArgs { unsigned char* p[SHIFT_MAX]; long long row_bytes[SHIFT_MAX]; long long first[SHIFT_MAX + 1]; int width[SHIFT_MAX]; int count; };
 
@@ -351,6 +379,28 @@ int devo_graph_append(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old
   hipLaunchKernelGGL(k_append, dim3(blocks_for(work, TB, 8192)), dim3(TB), 0, (hipStream_t)stream, ii, jj, kk, (const uint4*)net_old, (uint4*)net_new, ix,
                      ix_len, patch_ids, frame_ids, E, n_new, cpr);
   return check_launch("devo_graph_append");
+}
+
+int64_t devo_odom_append_frame_edges(int M, int n, int lifetime) {
+  if (M <= 0 || n < 1 || lifetime < 1) return 0;
+  const long long f0 = std::max(n - lifetime, 0);
+  return (long long)M * (n - 1 - f0) + (long long)M * (n - f0);
+}
+
+int devo_odom_append_frame(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old, void* net_new, const int64_t* ix, int64_t ix_len, int M, int n,
+                            int lifetime, int E, int capacity, int dim, int net_dtype, devo_stream_t stream) {
+  DEVO_REQUIRE(E >= 0 && ix_len >= 0 && M > 0, "devo_odom_append_frame: bad sizes");
+  DEVO_REQUIRE(n >= 1 && lifetime >= 1, "devo_odom_append_frame: a state of n = %d frames with a patch lifetime of %d has no window edges", n, lifetime);
+  DEVO_REQUIRE((long long)M * n <= INT32_MAX, "devo_odom_append_frame: more than 2^31 patches");
+  const long long n_new = devo_odom_append_frame_edges(M, n, lifetime);
+  DEVO_REQUIRE(E + n_new <= capacity, "devo_odom_append_frame: %d + %lld edges exceed the capacity %d", E, n_new, capacity);
+  DEVO_REQUIRE(ii && jj && kk && ix, "devo_odom_append_frame: null buffers");
+  int cpr = 0;
+  if (int rc = check_net("devo_odom_append_frame", net_old, net_new, dim, net_dtype, &cpr)) return rc;
+  const long long work = std::max<long long>((E + n_new) * cpr, n_new);
+  hipLaunchKernelGGL(k_append_frame, dim3(blocks_for(work, TB, 8192)), dim3(TB), 0, (hipStream_t)stream, ii, jj, kk, (const uint4*)net_old, (uint4*)net_new, ix,
+                     ix_len, frame_edges(M, n, lifetime), E, cpr);
+  return check_launch("devo_odom_append_frame");
 }
 
 int devo_graph_shift_frames(void* const* tensors, const int64_t* row_bytes, int count, int k, int n, devo_stream_t stream) {

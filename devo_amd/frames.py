@@ -5,6 +5,9 @@ reference runs these as small eager ops (five lietorch launches for one pose, a 
 pixel) with `.item()` round trips and a recursive Python walk per frame; here each is one launch (terminate(): 1 + ceil(log2(counter))),
 and the only wait is `Trajectory.complete`'s, behind its last kernel.  This is NOT a drop-in under a reference module name (the reference
 has no extension here): INTEGRATION.md shows the `DEVO` lines rewritten over these calls.  No CPU fallback.
+`frame_input` (the density gate, the normalisation and the 346-column crop of devo.py:406-467, two launches) and `probe_median` (the
+quantile of :256, one) over csrc/frame_input.hip are the pieces of `__call__` in front of the Patchifier and behind the motion probe;
+odometry.DEVO strings all of them together.
 
 The frame buffers are the caller's (devo.py:56-65): poses fp32 [N, 7], patches fp32 [N, M, 3, P, P], intrinsics fp32 [N, 4], tstamps int64
 [N] — or their `[1, ...]` views; they are written through raw pointers, so they must be contiguous and of these dtypes (nothing is
@@ -121,6 +124,88 @@ def point_cloud(poses, patches, intrinsics, ix, m, out, start_frame=0):
                                                 L.stream())
             L.check(rc, "frames.point_cloud")
     _bump(out)
+
+
+_NORMS = {"none": 0, "rescale": 1, "norm": 1, "standard": 2, "std": 2}      # DEVO_INPUT_*; the names of devo.py:420-438
+CROP_WIDTH = 346              # DEVO_INPUT_CROP_WIDTH (devo.py:466-467)
+PROBE_MEDIAN_MAX = 1024       # DEVO_PROBE_MEDIAN_MAX
+
+
+def pinned_record():
+    """A record for frame_input: 4 pinned doubles the kernels write through their host address."""
+    return torch.zeros(4, dtype=torch.float64).pin_memory()
+
+
+def _host_visible(what, t, dtype, n, name):
+    if not isinstance(t, torch.Tensor) or not (t.is_cuda or t.is_pinned()) or t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
+        raise ValueError(f"frames.{what}: {name} must be a contiguous {dtype} tensor of at least {n} elements on the GPU or in pinned host memory")
+
+
+def frame_input(voxel, norm="std", gate=False, out=None, record=None):
+    """devo.py:406-467 for one voxel grid [bins, H, W] (fp32 or fp16) -> (out fp32 [1, 1, bins, H, W'], record): the normalisation `norm`
+    ("none"; "rescale" / "norm": positives divided by the largest positive, negatives by minus the smallest negative, true fp32 divisions,
+    an absent polarity changes nothing; "std" / "standard": (x - mean) / sigma on the non-zero voxels, 0 elsewhere, mean and sigma exact to
+    fp64 and rounded once; a grid without a non-zero voxel is returned as it is) and the crop W' = W - 2 of a 346-column grid (columns
+    1 .. 344; the statistics include the two dropped columns, as the reference normalises first).  Two launches, no wait.
+    record: 4 pinned doubles {nnz = #(x != 0), numel, c0, c1} ((mean, sigma) under std, (largest positive, largest -negative) under
+    rescale), written behind the second launch: a caller that wants them records an event on the stream and waits for it — with
+    gate=True (the tracker's n == 0) it does, for the reference's test `nnz / numel < 2e-2` (devo.py:413); `gate` itself changes nothing
+    in what is launched.  Where all non-zero voxels are equal (sigma = 0) the result is events.std's for that grid.
+    The reference's "empty voxel" return (devo.py:432-435) cannot be reached — a maximum over positives and a minimum over negatives
+    are never 0, and a missing polarity is replaced by 1 — and is not built."""
+    L.require_gpu(voxel)
+    code = _NORMS.get(str(norm).lower())
+    if code is None:
+        raise NotImplementedError(f"frames.frame_input: norm {norm!r} is not implemented: one of {sorted(_NORMS)}")
+    if voxel.dim() != 3 or voxel.dtype not in (torch.float32, torch.float16) or voxel.numel() == 0:
+        raise ValueError(f"frames.frame_input: the voxel grid must be a non-empty fp32 or fp16 [bins, H, W] tensor, got {voxel.dtype} {tuple(voxel.shape)}")
+    voxel = voxel.contiguous()
+    bins, H, W = voxel.shape
+    Wout = W - 2 if W == CROP_WIDTH else W
+    if out is None:
+        out = torch.empty(1, 1, bins, H, Wout, dtype=torch.float32, device=voxel.device)
+    else:
+        L.require_gpu(out)
+        _same_device("frame_input", voxel, out)
+        if out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != bins * H * Wout:
+            raise ValueError(f"frames.frame_input: out must be a contiguous float32 tensor of {bins} x {H} x {Wout} elements")
+    if record is None:
+        record = pinned_record()
+    _host_visible("frame_input", record, torch.float64, 4, "record")
+    nat = backends.native()
+    with torch.cuda.device(voxel.device):
+        ws = torch.empty(L.lib().devo_odom_input_workspace_bytes(voxel.numel()), dtype=torch.uint8, device=voxel.device)
+        if nat is not None:
+            nat.frames.frame_input(voxel, code, out, ws, record)
+        else:
+            rc = L.lib().devo_odom_input(L.ptr(voxel), L.dtype_code(voxel), bins, H, W, code, L.ptr(out), L.ptr(ws), ws.numel(), L.ptr(record), L.stream())
+            L.check(rc, "frames.frame_input")
+    _bump(out)
+    return out.view(1, 1, bins, H, Wout), record
+
+
+def probe_median(delta, out=None):
+    """torch.quantile(delta.norm(dim=-1).float(), 0.5) of the motion probe (devo.py:256) for delta [1, M, 2], fp32 or fp16, one launch of
+    one workgroup -> fp32 [1] (`out`: a GPU tensor, or a pinned host tensor for a caller that reads it behind an event).  The norms are
+    formed in fp64 from the exactly converted input and rounded to fp32, the selection is exact, and for even M the mean of the two
+    middle values is formed in fp64 and rounded once."""
+    L.require_gpu(delta)
+    if delta.dtype not in (torch.float32, torch.float16) or delta.numel() == 0 or delta.shape[-1] != 2:
+        raise ValueError(f"frames.probe_median: delta must be a non-empty fp32 or fp16 [1, M, 2] tensor, got {delta.dtype} {tuple(delta.shape)}")
+    delta = delta.contiguous()
+    M = delta.numel() // 2
+    if M > PROBE_MEDIAN_MAX:
+        raise RuntimeError(f"frames.probe_median: the median over {M} values exceeds the supported {PROBE_MEDIAN_MAX}")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=delta.device)
+    _host_visible("probe_median", out, torch.float32, 1, "out")
+    nat = backends.native()
+    with torch.cuda.device(delta.device):
+        if nat is not None:
+            nat.frames.probe_median(delta, out)
+        else:
+            L.check(L.lib().devo_odom_probe_median(L.ptr(delta), L.dtype_code(delta), M, L.ptr(out), L.stream()), "frames.probe_median")
+    return out
 
 
 class Trajectory:

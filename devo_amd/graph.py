@@ -158,6 +158,37 @@ class PatchGraph:
         self._net = net_new
         self._views = None
 
+    # ------------------------------------------------------------------------------------------ devo.py:366-380, :541-542
+    def append_frame(self, n, lifetime, ix):
+        """The window edges of a new frame, for a state of n frames (after the increment of devo.py:537): append_factors(*edges_forw)
+        followed by append_factors(*edges_back) with r = lifetime — patches M max(n - r, 0) .. M (n - 1) - 1 -> frame n - 1, then patches
+        M (n - 1) .. M n - 1 -> frames max(n - r, 0) .. n - 1 in flatmeshgrid's `ij` order.  The ids are computed in the kernel: one
+        launch, no index lists, no wait; the graph is what two `append` calls with the torch-built lists leave."""
+        self._ready("append_frame", ix)
+        n, lifetime = int(n), int(lifetime)
+        if n < 1 or lifetime < 1:
+            raise ValueError(f"PatchGraph.append_frame: a state of n = {n} frames with a patch lifetime of {lifetime} has no window edges")
+        nat = backends.native()
+        n_new = int(nat.patch_graph.append_frame_edges(self.M, n, lifetime) if nat is not None else L.lib().devo_odom_append_frame_edges(self.M, n, lifetime))
+        E = self._E
+        if E + n_new > self.capacity:
+            raise RuntimeError(f"PatchGraph.append_frame: {E} + {n_new} edges exceed the capacity {self.capacity}")
+        if ix.dtype != torch.int64 or not ix.is_contiguous():
+            ix = ix.reshape(-1).long().contiguous()
+        b = self._buf[self._cur]
+        net_new = torch.empty(1, E + n_new, self.dim, dtype=self._net.dtype, device=b.device)
+        with torch.cuda.device(b.device):
+            if nat is not None:
+                nat.patch_graph.append_frame(b[0], b[1], b[2], self._net, net_new, ix, self.M, n, lifetime, E)
+            else:
+                rc = L.lib().devo_odom_append_frame(L.ptr(b[0]), L.ptr(b[1]), L.ptr(b[2]), L.ptr(self._net), L.ptr(net_new), L.ptr(ix), ix.numel(), self.M, n, lifetime, E,
+                                                    self.capacity, self.dim, L.dtype_code(net_new), L.stream())
+                L.check(rc, "PatchGraph.append_frame")
+        _bump(b)
+        self._E = E + n_new
+        self._net = net_new
+        self._views = None
+
     # ------------------------------------------------------------------------------------------ devo.py:235-239
     def remove(self, mask):
         """remove_factors(mask): ii, jj, kk = x[~mask], net = net[:, ~mask], order kept.  Waits once (for the new edge count)."""

@@ -43,7 +43,8 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   devo_traj_eval_workspace_bytes; and devo_camera_undistort_points, devo_camera_distort_points, devo_image_remap;
                                   and devo_esim_count, devo_esim_emit, devo_esim_sort_keys, devo_esim_sort_workspace_bytes, devo_esim_decode, devo_esim_max_span_ns,
                                   devo_log_intensity; and devo_optim_chunks, devo_optim_moment_elems, devo_optim_workspace_bytes, devo_optim_plan,
-                                  devo_optim_step);
+                                  devo_optim_step; and devo_odom_input, devo_odom_input_workspace_bytes, devo_odom_probe_median,
+                                  devo_odom_append_frame, devo_odom_append_frame_edges);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -746,6 +747,15 @@ int devo_graph_remove(const int64_t* ii, const int64_t* jj, const int64_t* kk, c
 int devo_graph_append(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old, void* net_new, const int64_t* ix, int64_t ix_len,
                       const int64_t* patch_ids, const int64_t* frame_ids, int E, int n_new, int capacity, int dim, int net_dtype, devo_stream_t stream);
 
+/* The window edges of a new frame (devo.py:366-380 followed by both append_factors calls of :541-542), ONE launch, for a state of n >= 1
+ * frames of M patches (after the increment of :537), r = lifetime >= 1: first the forward edges, patches M max(n - r, 0) .. M (n - 1) - 1
+ * -> frame n - 1, then the backward edges, patches M (n - 1) .. M n - 1 -> frames max(n - r, 0) .. n - 1 (patch-major: flatmeshgrid's
+ * `ij` order); ii = ix[kk] (-1 for a patch outside ix); net_new as in devo_graph_append.  devo_odom_append_frame_edges: how many
+ * edges that is (0 for arguments outside their ranges).  E + edges > capacity is an error (nothing is launched). */
+int64_t devo_odom_append_frame_edges(int M, int n, int lifetime);
+int devo_odom_append_frame(int64_t* ii, int64_t* jj, int64_t* kk, const void* net_old, void* net_new, const int64_t* ix, int64_t ix_len, int M, int n,
+                            int lifetime, int E, int capacity, int dim, int net_dtype, devo_stream_t stream);
+
 /* The frame shift of keyframe removal (devo.py:289-295) for up to DEVO_GRAPH_SHIFT_MAX tensors of any dtype in one launch: tensor s
  * is `tensors[s]` (HOST array of device pointers), contiguous, with rows of row_bytes[s] (HOST array) bytes; rows k + 1 .. n - 1 of
  * each move down by one (row r <- row r + 1 for r = k .. n - 2, in place). */
@@ -796,6 +806,31 @@ size_t devo_frame_complete_workspace_bytes(int counter);
 int devo_frame_complete_launches(int counter);
 int devo_frame_complete(const float* poses, const int64_t* tstamps, int n, int counter, const int64_t* parent, const float* rel, int capacity, float* out,
                         void* ws, size_t ws_bytes, int* status, devo_stream_t stream);
+
+/* A new voxel grid on its way to the Patchifier (devo.py:406-467), TWO launches, no host wait.  vox: fp32 or fp16 [bins, H, W];
+ * out: f32 [bins, H, W'], W' = W - 2 for W == DEVO_INPUT_CROP_WIDTH (columns 1 .. W - 2 are kept; the statistics are taken over all W
+ * columns, as the reference normalises before it crops), else W.
+ *   DEVO_INPUT_NONE     out = x.
+ *   DEVO_INPUT_RESCALE  positives divided by the largest positive, negatives by minus the smallest negative (correctly rounded fp32
+ *                       divisions); a polarity without entries changes nothing.
+ *   DEVO_INPUT_STD      with nnz = #(x != 0) > 0: out = (x - mean) / sigma on the non-zero voxels and 0 elsewhere, mean = sum x / nnz and
+ *                       sigma^2 = sum x^2 / nnz - mean^2 formed in fp64 and rounded to fp32 once, the difference and the quotient in fp32;
+ *                       nnz == 0: out = x.  Where all non-zero voxels are equal the result is devo_voxel_std's for that grid.
+ * record: 4 HOST-VISIBLE doubles (pinned host memory): {nnz, bins H W, c0, c1}, (c0, c1) = (mean, sigma) as fp32 values under STD, (largest
+ * positive, largest -negative) under RESCALE, zeros under NONE; valid once the work enqueued on `stream` so far has run.  Sums are fp64 in
+ * an order fixed by bins H W: the same bits from run to run.  ws: devo_odom_input_workspace_bytes(bins H W). */
+enum { DEVO_INPUT_NONE = 0, DEVO_INPUT_RESCALE = 1, DEVO_INPUT_STD = 2 };
+#define DEVO_INPUT_CROP_WIDTH 346
+size_t devo_odom_input_workspace_bytes(int64_t numel);
+int devo_odom_input(const void* vox, int dtype, int bins, int H, int W, int norm, float* out, void* ws, size_t ws_bytes, double* record,
+                     devo_stream_t stream);
+
+/* The motion probe's median (devo.py:256), ONE workgroup: out[0] = torch.quantile(delta.norm(dim=-1).float(), 0.5) for delta fp32 or fp16
+ * [M, 2], 1 <= M <= DEVO_PROBE_MEDIAN_MAX (beyond it DEVO_ERR_UNSUPPORTED, nothing is launched).  The norms are formed in fp64 from the
+ * exactly converted input and rounded to fp32; an exact selection; for even M the mean of the two middle values, formed in fp64 and rounded
+ * once; NaN if there is one.  out: f32, device or host-visible memory. */
+#define DEVO_PROBE_MEDIAN_MAX 1024
+int devo_odom_probe_median(const void* delta, int dtype, int M, float* out, devo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * The training loss of one update iteration (train.py:172-236 and the metrics of :254-266); T = fp32 or fp64 throughout.
