@@ -180,6 +180,10 @@ _SIGNATURES.update({
     "devo_traj_eval": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _d, _i, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
 })
 _SIGNATURES.update({
+    "devo_traj_rel_workspace_bytes": [_i64, _i, _i, _i],
+    "devo_traj_rel_eval": [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _d, _dp, _i, _i, _i, _i, _i, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp],
+})
+_SIGNATURES.update({
     "devo_camera_undistort_points": [_vp, _i64, _i, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _vp, _i, _vp, _vp],
     "devo_camera_distort_points": [_vp, _i64, _i, _i, _i, _i, _dp, _dp, _i, _dp, _dp, _vp, _i, _vp, _vp],
     "devo_image_remap": [_vp, _i, _i, _i, _i, _i, _vp, _i, _i, _vp, _i, _vp],
@@ -216,7 +220,7 @@ _RESTYPE = {"devo_last_error": ctypes.c_char_p, "devo_instnorm_workspace_bytes":
              "devo_voxel_hot_pixels_workspace_bytes": _sz, "devo_voxel_rescale_workspace_bytes": _sz, "devo_voxel_augment_workspace_bytes": _sz, "devo_depth_normalise_workspace_bytes": _sz, "devo_ba_workspace_bytes": _sz, "devo_neighbors_workspace_bytes": _sz,
              "devo_corr_backward_workspace_bytes": _sz, "devo_corr_patch_operand_bytes": _sz, "devo_upd_split_weight_bytes": _sz, "devo_upd_dw_workspace_bytes": _sz, "devo_upd_pack_weight_f16_bytes": _sz, "devo_upd_mlp2_weight_bytes": _sz, "devo_upd_rs_weight_bytes": _sz, "devo_upd_rs_split_weight_bytes": _sz, "devo_graph_workspace_bytes": _sz, "devo_loss_state_bytes": _sz,
              "devo_frame_complete_workspace_bytes": _sz, "devo_odom_input_workspace_bytes": _sz, "devo_odom_append_frame_edges": _i64, "devo_train_graph_workspace_bytes": _sz, "devo_frame_graph_workspace_bytes": _sz,
-             "devo_traj_eval_workspace_bytes": _sz, "devo_esim_max_span_ns": _i64, "devo_esim_sort_workspace_bytes": _sz,
+             "devo_traj_eval_workspace_bytes": _sz, "devo_traj_rel_workspace_bytes": _sz, "devo_esim_max_span_ns": _i64, "devo_esim_sort_workspace_bytes": _sz,
              "devo_optim_chunks": _i64, "devo_optim_moment_elems": _i64, "devo_optim_workspace_bytes": _sz}
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)

@@ -17,7 +17,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 LIB = os.path.join(LIBDIR, "libdevo_hip.so")
-SOURCES = ["abi.hip", "lie.hip", "corr.hip", "ba.hip", "ba_tables.hip", "transform.hip", "update.hip", "linear.hip", "linear_dw.hip", "mlp2.hip", "gemm_rs.hip", "events.hip", "data.hip", "graph.hip", "loss.hip", "frames.hip", "frame_input.hip", "train_graph.hip", "frame_graph.hip", "select.hip", "traj_eval.hip", "camera.hip", "esim.hip", "optim.hip"]
+SOURCES = ["abi.hip", "lie.hip", "corr.hip", "ba.hip", "ba_tables.hip", "transform.hip", "update.hip", "linear.hip", "linear_dw.hip", "mlp2.hip", "gemm_rs.hip", "events.hip", "data.hip", "graph.hip", "loss.hip", "frames.hip", "frame_input.hip", "train_graph.hip", "frame_graph.hip", "select.hip", "traj_eval.hip", "traj_rel.hip", "camera.hip", "esim.hip", "optim.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function", "-Wno-pass-failed", "-fno-slp-vectorize"]
 
 

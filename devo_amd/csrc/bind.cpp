@@ -873,6 +873,46 @@ TensorList traj_eval(const Tensor& est, const Tensor& est_stamps, const Tensor& 
   return {stats, transform, status, errors, matched};
 }
 
+// devo_traj_rel_eval on the same tensors (csrc/traj_rel.hip): deltas are host numbers, scale_mode DEVO_TRAJ_REL_SCALE_* with `scale` (VALUE) or
+// `scales` f64 [B] on the GPU (PER_PAIR).
+// -> {stats f64 [B, D, DEVO_TRAJ_REL_COLS], status i32 [B, D], errors f64 [D, total_est, 2] or [0], ends i32 [D, total_est] or [0]}
+TensorList traj_rel_eval(const Tensor& est, const Tensor& est_stamps, const Tensor& est_off, const Tensor& gt, const Tensor& gt_stamps, const Tensor& gt_off, int64_t assoc,
+                         double max_diff, std::vector<double> deltas, int64_t unit, bool relative, int64_t along, int64_t end, int64_t scale_mode, double scale,
+                         const c10::optional<Tensor>& scales, bool want_errors) {
+  require_gpu(est, est_stamps, est_off, gt, gt_stamps, gt_off);
+  for (const Tensor* t : {&est, &gt})
+    TORCH_CHECK(t->dim() == 2 && t->size(1) == 7 && t->is_contiguous() && (t->scalar_type() == at::kFloat || t->scalar_type() == at::kDouble) &&
+                t->scalar_type() == est.scalar_type() && t->device() == est.device(), "evaluation: poses must be contiguous [N, 7] tensors of one dtype (float32 or float64) on one GPU");
+  for (const Tensor* t : {&est_stamps, &gt_stamps})
+    TORCH_CHECK(t->dim() == 1 && t->is_contiguous() && (t->scalar_type() == at::kLong || t->scalar_type() == at::kDouble) && t->scalar_type() == est_stamps.scalar_type() &&
+                t->device() == est.device(), "evaluation: stamps must be contiguous [N] tensors of one dtype (int64 or float64) on the poses' GPU");
+  TORCH_CHECK(est_stamps.numel() == est.size(0) && gt_stamps.numel() == gt.size(0), "evaluation: one stamp per pose expected");
+  pg_check_idx("evaluation", est_off);
+  pg_check_idx("evaluation", gt_off);
+  const int64_t B = est_off.numel() - 1, D = (int64_t)deltas.size();
+  TORCH_CHECK(B >= 1 && gt_off.numel() == B + 1 && B <= INT32_MAX / DEVO_TRAJ_REL_MAX_DELTAS && est_off.device() == est.device() && gt_off.device() == est.device(),
+              "evaluation: offsets must be two int64 [B + 1] tensors on the poses' GPU");
+  TORCH_CHECK(D >= 1 && D <= DEVO_TRAJ_REL_MAX_DELTAS, "evaluation: 1 .. ", DEVO_TRAJ_REL_MAX_DELTAS, " deltas expected (", D, ")");
+  const bool per_pair = scale_mode == DEVO_TRAJ_REL_SCALE_PER_PAIR;
+  TORCH_CHECK(!per_pair || (scales.has_value() && scales->defined() && scales->is_cuda() && scales->device() == est.device() && scales->scalar_type() == at::kDouble &&
+                            scales->dim() == 1 && scales->numel() == B && scales->is_contiguous()),
+              "evaluation: one scale per pair expected, a contiguous float64 [B] tensor on the poses' GPU");
+  c10::DeviceGuard guard(est.device());
+  const auto fo = est.options().dtype(at::kDouble).memory_format(c10::nullopt);
+  const int64_t total_est = est.size(0);
+  Tensor stats = at::empty({B, D, DEVO_TRAJ_REL_COLS}, fo), status = at::empty({B, D}, fo.dtype(at::kInt));
+  Tensor errors = want_errors ? at::empty({D, total_est, 2}, fo) : at::empty({0}, fo);
+  Tensor ends = want_errors ? at::empty({D, total_est}, fo.dtype(at::kInt)) : at::empty({0}, fo.dtype(at::kInt));
+  const size_t bytes = devo_traj_rel_workspace_bytes(total_est, (int)assoc, (int)B, (int)D);
+  Tensor ws = at::empty({(int64_t)bytes}, fo.dtype(at::kByte));
+  check(devo_traj_rel_eval(est.data_ptr(), est_stamps.data_ptr(), i64p(est_off), total_est, gt.data_ptr(), gt_stamps.data_ptr(), i64p(gt_off), gt.size(0), (int)B,
+                           dtype_code(est), est_stamps.scalar_type() == at::kDouble ? 1 : 0, (int)assoc, max_diff, deltas.data(), (int)D, (int)unit, relative ? 1 : 0,
+                           (int)along, (int)end, (int)scale_mode, scale, per_pair ? scales->data_ptr<double>() : nullptr, stats.data_ptr<double>(),
+                           status.data_ptr<int>(), want_errors ? errors.data_ptr<double>() : nullptr, want_errors ? ends.data_ptr<int>() : nullptr, ws.data_ptr(),
+                           bytes, stream_of(est)), "evaluation");
+  return {stats, status, errors, ends};
+}
+
 // ------------------------------------------------------------------------------------------------ camera models (devo_amd/camera.py; csrc/camera.hip)
 // devo_camera_undistort_points / devo_camera_distort_points on tensors: points [n, 2] (fp32 or fp64) or none (the H x W pixel grid, on GPU
 // `device`); K (4), dist, R (9 or empty), K_new (4 or empty) are host numbers.  -> {out [n, 2] or [H, W, 2], invalid i32 [1] or [0]}
@@ -1237,6 +1277,8 @@ TORCH_LIBRARY(devo_hip, m) {
         "int cy0, int cy1, Tensor? disps, int P) -> Tensor[]");
   m.def("traj_eval(Tensor est, Tensor est_stamps, Tensor est_off, Tensor gt, Tensor gt_stamps, Tensor gt_off, int assoc, int align, float max_diff, int rpe_delta, "
         "bool want_errors, bool want_matched) -> Tensor[]");
+  m.def("traj_rel_eval(Tensor est, Tensor est_stamps, Tensor est_off, Tensor gt, Tensor gt_stamps, Tensor gt_off, int assoc, float max_diff, float[] deltas, int unit, "
+        "bool relative, int along, int end, int scale_mode, float scale, Tensor? scales, bool want_errors) -> Tensor[]");
   m.def("camera_points(Tensor? points, int H, int W, int device, int model, float[] K, float[] dist, float[] R, float[] K_new, bool distort, bool out_f64, bool count) "
         "-> Tensor[]");
   m.def("image_remap(Tensor images, Tensor map, Tensor? out, bool out_u8) -> Tensor");
@@ -1274,6 +1316,7 @@ TORCH_LIBRARY_IMPL(devo_hip, CompositeExplicitAutograd, m) {
   m.impl("frame_graph_lists", &fg_lists);
   m.impl("patch_select", &patch_select);
   m.impl("traj_eval", &traj_eval);
+  m.impl("traj_rel_eval", &traj_rel_eval);
   m.impl("camera_points", &camera_points);
   m.impl("image_remap", &image_remap);
   m.impl("esim_count", &esim_count);
@@ -1356,6 +1399,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   ev.def("traj_eval", &traj_eval);
   ev.def("workspace_bytes", [](int64_t total_est, int64_t assoc) { return (int64_t)devo_traj_eval_workspace_bytes(total_est, (int)assoc); });
   ev.attr("COLS") = (int64_t)DEVO_TRAJ_EVAL_COLS;
+  ev.def("traj_rel_eval", &traj_rel_eval);
+  ev.def("rel_workspace_bytes", [](int64_t total_est, int64_t assoc, int64_t B, int64_t D) {
+    return (int64_t)devo_traj_rel_workspace_bytes(total_est, (int)assoc, (int)B, (int)D);
+  });
+  ev.attr("REL_COLS") = (int64_t)DEVO_TRAJ_REL_COLS;
   ev.attr("MAX_MATCHES") = (int64_t)DEVO_TRAJ_EVAL_MAX_MATCHES;
   auto cam = m.def_submodule("camera", "devo_amd.camera: rectification maps, point (un)distortion and image remap (what the reference takes from OpenCV)");
   cam.def("points", &camera_points);

@@ -24,7 +24,13 @@ transform; with check=True (one read-back of `status`) it raises instead, naming
 No CPU fallback: CPU tensors raise; numpy arrays are uploaded.  One launch per call, on the current stream; the only host synchronisation
 is the status read-back of check=True.  Lists of tensors are packed on the device (one concatenation each); the offsets are built on the
 host and uploaded (one small copy).
+
+`relative_errors` (csrc/traj_rel.hip) is the relative pose error over sub-trajectories of given lengths in frames, seconds, metres, radians
+or degrees: what the reference's scripts/evaluate_rpe.py computes for a fixed delta and what its log_results calls the "rel stats".  See the
+function; REL_COLUMNS are the columns of `RelativeResult.stats` (fp64 [B, D, 16]).
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -125,19 +131,9 @@ def _host_offsets(o, total, what):
     return o
 
 
-def evaluate(est, est_stamps, gt, gt_stamps, *, max_diff, align="sim3", association="nearest", rpe_delta=0, offsets=None, return_errors=False, return_matches=False,
-             check=True):
-    """One pair (est [Ne, 7], est_stamps [Ne], gt [Ng, 7], gt_stamps [Ng]), lists of those (one entry per pair), or packed tensors with
-    offsets=(est_offsets, gt_offsets), two host sequences of B + 1 row offsets.  max_diff is in the stamps' unit.  -> Result."""
-    if align not in ALIGN:
-        raise ValueError(f"evaluate: align {align!r} (have: none, se3, sim3)")
-    if association not in ASSOCIATION:
-        raise ValueError(f"evaluate: association {association!r} (have: nearest, interpolate)")
-    max_diff, rpe_delta = float(max_diff), int(rpe_delta)
-    if association == "nearest" and not max_diff >= 0.0:
-        raise ValueError("evaluate: max_diff must be >= 0")
-    if rpe_delta < 0:
-        raise ValueError("evaluate: rpe_delta must be >= 0")
+def _inputs(est, est_stamps, gt, gt_stamps, offsets):
+    """what `evaluate` and `relative_errors` accept -> packed device tensors of matching dtypes and the host offsets:
+    (est, est_stamps, gt, gt_stamps, est_offsets, gt_offsets)"""
     for stamps in (est_stamps, gt_stamps):                         # what the host can see of the stamps, before anything is uploaded
         for t in (stamps if isinstance(stamps, (list, tuple)) else (stamps,)):
             if isinstance(t, np.ndarray) and t.size and not float(np.abs(t.astype(np.float64)).max()) < _STAMP_LIMIT:
@@ -182,10 +178,27 @@ def evaluate(est, est_stamps, gt, gt_stamps, *, max_diff, align="sim3", associat
             raise ValueError("evaluate: the two offset vectors must have the same length B + 1")
     else:
         eo, go = [0, est.shape[0]], [0, gt.shape[0]]
+    return est.contiguous(), est_stamps.contiguous(), gt.contiguous(), gt_stamps.contiguous(), eo, go
+
+
+def evaluate(est, est_stamps, gt, gt_stamps, *, max_diff, align="sim3", association="nearest", rpe_delta=0, offsets=None, return_errors=False, return_matches=False,
+             check=True):
+    """One pair (est [Ne, 7], est_stamps [Ne], gt [Ng, 7], gt_stamps [Ng]), lists of those (one entry per pair), or packed tensors with
+    offsets=(est_offsets, gt_offsets), two host sequences of B + 1 row offsets.  max_diff is in the stamps' unit.  -> Result."""
+    if align not in ALIGN:
+        raise ValueError(f"evaluate: align {align!r} (have: none, se3, sim3)")
+    if association not in ASSOCIATION:
+        raise ValueError(f"evaluate: association {association!r} (have: nearest, interpolate)")
+    max_diff, rpe_delta = float(max_diff), int(rpe_delta)
+    if association == "nearest" and not max_diff >= 0.0:
+        raise ValueError("evaluate: max_diff must be >= 0")
+    if rpe_delta < 0:
+        raise ValueError("evaluate: rpe_delta must be >= 0")
+    est, est_stamps, gt, gt_stamps, eo, go = _inputs(est, est_stamps, gt, gt_stamps, offsets)
+    dev = est.device
     B = len(eo) - 1
     interp = association == "interpolate"
     short_is_est = [interp or (eo[b + 1] - eo[b]) < (go[b + 1] - go[b]) for b in range(B)]
-    est, gt, est_stamps, gt_stamps = est.contiguous(), gt.contiguous(), est_stamps.contiguous(), gt_stamps.contiguous()
     total_est = est.shape[0]
     with torch.cuda.device(dev):
         off = torch.tensor([eo, go], dtype=torch.int64).to(dev, non_blocking=True)
@@ -261,3 +274,133 @@ def summary(results_by_scene, dataset_name=None):
     out["AUC"] = float(torch.clamp(1.0 - torch.cat(everything), min=0.0).mean())
     out["AVG"] = sum(medians) / len(medians) / 100.0
     return out
+
+
+# ---------------------------------------------------------------------------------------------------------------- relative pose error
+REL_COLUMNS = ("n", "trans_rmse", "trans_mean", "trans_median", "trans_std", "trans_min", "trans_max", "rot_rmse_deg", "rot_mean_deg", "rot_median_deg",
+               "rot_std_deg", "rot_min_deg", "rot_max_deg", "delta", "span_mean", "scale")      # DEVO_TRAJ_REL_COLS
+MAX_DELTAS = 16                                                    # DEVO_TRAJ_REL_MAX_DELTAS
+UNITS = {"f": 0, "s": 1, "m": 2, "rad": 3, "deg": 4}               # DEVO_TRAJ_REL_UNIT_*
+ALONG = {"gt": 0, "est": 1}                                        # DEVO_TRAJ_REL_ALONG_*
+END = {"reach": 0, "closest": 1}                                   # DEVO_TRAJ_REL_END_*
+NO_PAIR = 128                                                      # DEVO_TRAJ_REL_NO_PAIR
+REL_FLAGS = dict(FLAGS)
+REL_FLAGS.update({2: "too few matches (three for scale=\"sim3\", two for a given scale)", 8: "the long trajectory's stamps, or the estimate's matched stamps, are not non-decreasing",
+                  NO_PAIR: "no sub-trajectory of this length (no pair of poses)"})
+
+
+class RelativeResult:
+    """stats fp64 [B, D, 16] (REL_COLUMNS; every column is an attribute: result.trans_rmse is stats[:, :, 1]), status int32 [B, D];
+    errors fp64 [D, total_est, 2] (|t_E|, the angle of R_E in degrees) / ends int32 [D, total_est] or None, packed like the estimate:
+    `errors_of(b, d)`, `ends_of(b, d)` give pair b's rows for delta d, row i for the sub-trajectory that starts at match i (NaN / -1
+    where there is none, and behind the number of matches); an end is a match number as well."""
+
+    def __init__(self, stats, status, errors, ends, est_offsets, unit):
+        self.stats, self.status, self.errors, self.ends, self.est_offsets, self.unit = stats, status, errors, ends, est_offsets, unit
+
+    def __getattr__(self, name):
+        if name in REL_COLUMNS:
+            return self.stats[:, :, REL_COLUMNS.index(name)]
+        raise AttributeError(name)
+
+    def __len__(self):
+        return self.stats.shape[0]
+
+    def _rows(self, t, b, d):
+        if t is None:
+            raise ValueError("relative_errors: ask for it (return_errors=True)")
+        return t[d, self.est_offsets[b]:self.est_offsets[b + 1]]
+
+    def errors_of(self, b=0, d=0):
+        return self._rows(self.errors, b, d)
+
+    def ends_of(self, b=0, d=0):
+        return self._rows(self.ends, b, d)
+
+    def percent(self):
+        """RPG's relative figures for unit "m" -> (100 trans_mean / delta in percent, rot_mean_deg / delta in degrees per metre), each [B, D]"""
+        if self.unit != "m":
+            raise ValueError(f"percent: the deltas are in {self.unit!r}, not in metres")
+        return 100.0 * self.trans_mean / self.delta, self.rot_mean_deg / self.delta
+
+
+def relative_errors(est, est_stamps, gt, gt_stamps, *, deltas, unit="m", relative=False, along="gt", end="reach", scale="sim3", max_diff, association="nearest",
+                    offsets=None, return_errors=False, check=True):
+    """The relative pose error over sub-trajectories of the lengths `deltas` (1 .. 16 positive numbers in `unit`: "f" frames, i.e. matches,
+    "s" the stamps' unit, "m", "rad", "deg"; with relative=True fractions of the whole index range, resolved on the device).  Inputs as for
+    `evaluate`; the stages for a pair:
+      1. association, exactly `evaluate`'s -> n matches (x_k, y_k, s_k) in short order, s_k the estimate's stamp;
+      2. the scale c of the estimate's relative translations: "sim3" (the Umeyama scale, `evaluate(align="sim3").scale`), a float for all
+         pairs, or a device tensor [B]; a given scale needs two matches and no alignment;
+      3. the index u_k: k, s_k, or the cumulative path length / rotation angle along the matched ground truth (along="gt", the RPG
+         convention) or the estimate (along="est", scripts/evaluate_rpe.py; its lengths times c);
+      4. the end j of the sub-trajectory that starts at i: end="reach", the first j > i with u_j - u_i >= delta; end="closest", the j
+         nearest to u_i + delta (the lowest on a tie), dropped when j = n - 1 (evaluate_rpe.py:263-266);
+      5. E = (c . (X_i^-1 X_j))^-1 (Y_i^-1 Y_j): |t_E| and the angle of R_E in degrees;
+      6. the statistics per (pair, delta) -> RelativeResult.
+    Three launches on the current stream (csrc/traj_rel.hip); the only host synchronisation is the status read-back of check=True, which
+    raises for a flagged pair or a (pair, delta) without a pair of poses, naming both."""
+    who = "relative_errors"
+    if association not in ASSOCIATION:
+        raise ValueError(f"{who}: association {association!r} (have: nearest, interpolate)")
+    if unit not in UNITS:
+        raise ValueError(f"{who}: unit {unit!r} (have: f, s, m, rad, deg)")
+    if along not in ALONG:
+        raise ValueError(f"{who}: along {along!r} (have: gt, est)")
+    if end not in END:
+        raise ValueError(f"{who}: end {end!r} (have: reach, closest)")
+    max_diff = float(max_diff)
+    if association == "nearest" and not max_diff >= 0.0:
+        raise ValueError(f"{who}: max_diff must be >= 0")
+    deltas = [float(v) for v in (deltas if isinstance(deltas, (list, tuple, np.ndarray)) else (deltas,))]
+    D = len(deltas)
+    if not 1 <= D <= MAX_DELTAS:
+        raise ValueError(f"{who}: 1 .. {MAX_DELTAS} deltas expected ({D})")
+    if not all(0.0 < v < float("inf") for v in deltas):
+        raise ValueError(f"{who}: deltas must be positive and finite ({deltas})")
+    B = len(est) if isinstance(est, (list, tuple)) else len(offsets[0]) - 1 if offsets is not None else 1      # (checked again by the packing)
+    scales, scale_value = None, 1.0
+    if isinstance(scale, str):
+        if scale != "sim3":
+            raise ValueError(f"{who}: scale {scale!r} (have: \"sim3\", a float, a device tensor [B])")
+        mode = 0
+    elif torch.is_tensor(scale):
+        if scale.dim() != 1 or scale.shape[0] != B or not scale.is_floating_point():
+            raise ValueError(f"{who}: a scale tensor must hold one floating-point number per pair ([{B}]), not {tuple(scale.shape)} of {scale.dtype}")
+        L.require_gpu(scale)
+        scales, mode = scale.double().contiguous(), 2
+    else:
+        scale_value, mode = float(scale), 1
+        if not 0.0 < scale_value < float("inf"):
+            raise ValueError(f"{who}: the scale must be positive and finite ({scale_value})")
+    est, est_stamps, gt, gt_stamps, eo, go = _inputs(est, est_stamps, gt, gt_stamps, offsets)
+    dev = est.device
+    if len(eo) - 1 != B or (scales is not None and scales.device != dev):
+        raise ValueError(f"{who}: one scale per pair on the poses' GPU expected")
+    total_est = est.shape[0]
+    with torch.cuda.device(dev):
+        off = torch.tensor([eo, go], dtype=torch.int64).to(dev, non_blocking=True)
+        nat = backends.native()
+        if nat is not None:
+            stats, status, errors, ends = nat.evaluation.traj_rel_eval(est, est_stamps, off[0], gt, gt_stamps, off[1], ASSOCIATION[association], max_diff, deltas,
+                                                                       UNITS[unit], bool(relative), ALONG[along], END[end], mode, scale_value, scales, bool(return_errors))
+        else:
+            stats = torch.empty((B, D, len(REL_COLUMNS)), dtype=torch.float64, device=dev)
+            status = torch.empty((B, D), dtype=torch.int32, device=dev)
+            errors = torch.empty((D, total_est, 2) if return_errors else 0, dtype=torch.float64, device=dev)
+            ends = torch.empty((D, total_est) if return_errors else 0, dtype=torch.int32, device=dev)
+            bytes_ = int(L.lib().devo_traj_rel_workspace_bytes(total_est, ASSOCIATION[association], B, D))
+            ws = torch.empty(bytes_, dtype=torch.uint8, device=dev)
+            rc = L.lib().devo_traj_rel_eval(L.ptr(est), L.ptr(est_stamps), L.ptr(off[0]), total_est, L.ptr(gt), L.ptr(gt_stamps), L.ptr(off[1]), gt.shape[0], B,
+                                            L.dtype_code(est), int(est_stamps.dtype == torch.float64), ASSOCIATION[association], max_diff, (ctypes.c_double * D)(*deltas), D,
+                                            UNITS[unit], int(bool(relative)), ALONG[along], END[end], mode, scale_value, L.ptr(scales), L.ptr(stats), L.ptr(status),
+                                            L.ptr(errors) if return_errors else None, L.ptr(ends) if return_errors else None, L.ptr(ws), bytes_, L.stream())
+            L.check(rc, who)
+        if check and not torch.cuda.is_current_stream_capturing():
+            for b, row in enumerate(status.tolist()):                                    # the one read-back
+                for d, s in enumerate(row):
+                    if s:
+                        why = "; ".join(text for bit, text in REL_FLAGS.items() if s & bit)
+                        raise RuntimeError(f"{who}: pair {b} ({eo[b + 1] - eo[b]} estimated, {go[b + 1] - go[b]} ground-truth poses), delta {d} ({deltas[d]:g} {unit}"
+                                           f"{', relative' if relative else ''}): {why}")
+    return RelativeResult(stats, status, errors if return_errors else None, ends if return_errors else None, eo, unit)

@@ -44,7 +44,7 @@ enum { DEVO_F32 = 0, DEVO_F16 = 1, DEVO_F64 = 2 };
                                   and devo_esim_count, devo_esim_emit, devo_esim_sort_keys, devo_esim_sort_workspace_bytes, devo_esim_decode, devo_esim_max_span_ns,
                                   devo_log_intensity; and devo_optim_chunks, devo_optim_moment_elems, devo_optim_workspace_bytes, devo_optim_plan,
                                   devo_optim_step; and devo_odom_input, devo_odom_input_workspace_bytes, devo_odom_probe_median,
-                                  devo_odom_append_frame, devo_odom_append_frame_edges);
+                                  devo_odom_append_frame, devo_odom_append_frame_edges; and devo_traj_rel_eval, devo_traj_rel_workspace_bytes);
                               callers compare with devo_abi_version() */
 int devo_abi_version(void);
 const char* devo_last_error(void); /* thread-local message of the last failing call */
@@ -1000,6 +1000,47 @@ size_t devo_traj_eval_workspace_bytes(int64_t total_est, int assoc);
 int devo_traj_eval(const void* est, const void* est_stamps, const int64_t* est_off, int64_t total_est, const void* gt, const void* gt_stamps,
                    const int64_t* gt_off, int64_t total_gt, int B, int pose_dtype, int stamps_f64, int assoc, int align, double max_diff, int rpe_delta,
                    double* stats, double* transform, int* status, double* errors_out, int* matched_out, void* ws, size_t ws_bytes, devo_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Relative pose error (the drift over sub-trajectories of a given length: what the reference's scripts/evaluate_rpe.py computes for a
+ * fixed delta, and the "rel stats" of utils/eval_utils.py:log_results; csrc/traj_rel.hip; devo_amd/evaluation.py: relative_errors).
+ * THREE launches on `stream`: devo_traj_eval's (association as above, align SIM3 when the scale is asked of it, NONE otherwise), prepare
+ * (one workgroup per pair) and errors (one workgroup per (pair, delta)); fp64, fixed-order reductions, bit-reproducible, independent of
+ * B and D, no host synchronisation.  est .. stamps_f64, assoc, max_diff: as for devo_traj_eval.  The n matches (x_k, y_k, s_k) of a pair
+ * are in short order; s_k is the estimate's stamp.
+ *   deltas       HOST fp64 [D], 1 <= D <= DEVO_TRAJ_REL_MAX_DELTAS, positive and finite; with relative != 0 fractions of u_{n-1} - u_0
+ *                (resolved on the device).
+ *   scale_mode   SIM3: c is the Umeyama scale of devo_traj_eval(align SIM3) (same bits; its rule of three matches and its degeneracy
+ *                flag apply); VALUE: c = scale for every pair; PER_PAIR: c = scale_per_pair[b] (DEVICE fp64 [B]).  With a given scale
+ *                two matches suffice (fewer: DEVO_TRAJ_TOO_FEW) and collinear matches are valid.
+ *   unit         the index u_k: FRAMES k; STAMPS s_k (must not decrease: DEVO_TRAJ_UNSORTED); METRES the cumulative path length,
+ *                RADIANS / DEGREES the cumulative rotation angle between consecutive matches, along the ground truth's matched poses
+ *                (ALONG_GT) or the estimate's (ALONG_EST; its lengths times c).
+ *   end          of the sub-trajectory that starts at match i.  REACH: the first j > i with u_j - u_i >= delta, none: no pair.  CLOSEST:
+ *                the j in [0, n) whose u_j is nearest to u_i + delta, the lowest on a tie; dropped when j = n - 1 (j = i can occur).
+ *   the error    E = (c . (X_i^-1 X_j))^-1 (Y_i^-1 Y_j), c multiplying the translation of the estimate's relative motion; |t_E| and the
+ *                angle of R_E in degrees, 2 atan2(|q_v|, |q_w|).
+ *   stats        fp64 [B, D, DEVO_TRAJ_REL_COLS]: 0 n (pose pairs); 1 trans_rmse, 2 trans_mean, 3 trans_median, 4 trans_std, 5 trans_min,
+ *                6 trans_max; 7 .. 12 the same of the rotation error in degrees; 13 delta (resolved, in the unit); 14 span_mean, the mean
+ *                of u_j - u_i; 15 scale c.  std and median as for devo_traj_eval.
+ *   status       i32 [B, D]: devo_traj_eval's flags of the pair in each of its rows (and TOO_FEW / UNSORTED as above), or
+ *                DEVO_TRAJ_REL_NO_PAIR for a (pair, delta) without a pair of poses.  A flagged row has n = 0 and NaN elsewhere.
+ *   errors_out   fp64 [D, total_est, 2] or NULL: (|t_E|, angle) of the sub-trajectory starting at match i, at row est_off[b] + i; NaN where
+ *                there is none.  ends_out i32 [D, total_est] or NULL: its end j (a match number), -1 likewise.
+ *   ws           devo_traj_rel_workspace_bytes(total_est, assoc, B, D) bytes, 16-byte aligned.
+ * ---------------------------------------------------------------------------------------------- */
+#define DEVO_TRAJ_REL_COLS 16
+#define DEVO_TRAJ_REL_MAX_DELTAS 16
+enum { DEVO_TRAJ_REL_UNIT_FRAMES = 0, DEVO_TRAJ_REL_UNIT_STAMPS = 1, DEVO_TRAJ_REL_UNIT_METRES = 2, DEVO_TRAJ_REL_UNIT_RADIANS = 3, DEVO_TRAJ_REL_UNIT_DEGREES = 4 };
+enum { DEVO_TRAJ_REL_ALONG_GT = 0, DEVO_TRAJ_REL_ALONG_EST = 1 };
+enum { DEVO_TRAJ_REL_END_REACH = 0, DEVO_TRAJ_REL_END_CLOSEST = 1 };
+enum { DEVO_TRAJ_REL_SCALE_SIM3 = 0, DEVO_TRAJ_REL_SCALE_VALUE = 1, DEVO_TRAJ_REL_SCALE_PER_PAIR = 2 };
+enum { DEVO_TRAJ_REL_NO_PAIR = 128 }; /* joins the DEVO_TRAJ_* status bits */
+size_t devo_traj_rel_workspace_bytes(int64_t total_est, int assoc, int B, int D);
+int devo_traj_rel_eval(const void* est, const void* est_stamps, const int64_t* est_off, int64_t total_est, const void* gt, const void* gt_stamps,
+                       const int64_t* gt_off, int64_t total_gt, int B, int pose_dtype, int stamps_f64, int assoc, double max_diff, const double* deltas,
+                       int D, int unit, int relative, int along, int end, int scale_mode, double scale, const double* scale_per_pair, double* stats,
+                       int* status, double* errors_out, int* ends_out, void* ws, size_t ws_bytes, devo_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Camera models (what the reference obtains from OpenCV: utils/load_utils.py:675-702, :1041-1058, scripts/pp_*.py, devo/stream.py:26,74;
