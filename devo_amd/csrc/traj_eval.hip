@@ -14,16 +14,15 @@
 //      digits, an LDS histogram with integer atomics, both middle ranks in the same sweeps.
 // Every reduction is per-thread strided partials, then wave shuffles, then LDS across the four waves, in a fixed order: no floating-point
 // atomics, bit-reproducible, independent of B.  Vector stores only.
-#include "common.h"
-#include <math.h>
+// The algebra, the reductions, the select (block_median), the match accessor (Matches) and the workspace layout (eval_ws) are traj_dev.h's,
+// shared with traj_rel.hip, whose launches read the matches this one leaves in its workspace.
+#include "traj_dev.h"
 
 namespace {
 
 using namespace devo;
+using namespace devo::traj;
 
-constexpr int TB = 256;
-constexpr int WAVES = TB / 64;
-constexpr int MAXR = 12;                       // values one reduction carries
 constexpr double RANK_RULE = 1e-10;            // sigma_2 <= RANK_RULE * sigma_1: degenerate
 constexpr double STAMP_LIMIT = 9007199254740992.0;   // 2^53
 
@@ -35,90 +34,6 @@ struct EvalArgs {
   int* mi; int* mj; double* err; double* ipose;
   double* stats; double* transform; int* status; double* errors_out; int* matched_out;
 };
-
-struct V3 { double x, y, z; };
-struct Q4 { double x, y, z, w; };
-
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double norm(V3 a) { return sqrt(dot(a, a)); }
-
-__device__ __forceinline__ Q4 qconj(Q4 q) { return {-q.x, -q.y, -q.z, q.w}; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-          a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-// the rotation of a unit quaternion applied to v: v + 2 w (u x v) + 2 u x (u x v)
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-  const V3 u = {q.x, q.y, q.z};
-  const V3 c = cross(u, v);
-  return v + 2.0 * (q.w * c + cross(u, c));
-}
-__device__ __forceinline__ double qangle_deg(Q4 q) {
-  return 2.0 * atan2(sqrt(q.x * q.x + q.y * q.y + q.z * q.z), fabs(q.w)) * (180.0 / 3.14159265358979323846);
-}
-
-template <typename T> __device__ __forceinline__ V3 load_pos(const T* __restrict__ p, long long i) {
-  return {(double)p[7 * i], (double)p[7 * i + 1], (double)p[7 * i + 2]};
-}
-template <typename T> __device__ __forceinline__ Q4 load_quat(const T* __restrict__ p, long long i) {
-  const double x = (double)p[7 * i + 3], y = (double)p[7 * i + 4], z = (double)p[7 * i + 5], w = (double)p[7 * i + 6];
-  const double r = 1.0 / sqrt(x * x + y * y + z * z + w * w);
-  return {x * r, y * r, z * r, w * r};
-}
-
-// K sums over the workgroup, every thread gets them: shuffles inside a wave, then the four waves' values added in order
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*sh)[MAXR]) {
-  static_assert(K <= MAXR, "block_sum: too many values");
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-  }
-  __syncthreads();                                                   // (the previous reduction's values have been read)
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; k++) sh[wv][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    double r = sh[0][k];
-#pragma unroll
-    for (int w = 1; w < WAVES; w++) r += sh[w][k];
-    v[k] = r;
-  }
-}
-
-// min and max alike (fmin / fmax skip a NaN; the caller sets both to NaN when the sums are)
-__device__ __forceinline__ void block_minmax(double& lo, double& hi, double (*sh)[MAXR]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_down(lo, o, 64));
-    hi = fmax(hi, __shfl_down(hi, o, 64));
-  }
-  __syncthreads();
-  if (lane == 0) { sh[wv][0] = lo; sh[wv][1] = hi; }
-  __syncthreads();
-  lo = sh[0][0]; hi = sh[0][1];
-#pragma unroll
-  for (int w = 1; w < WAVES; w++) { lo = fmin(lo, sh[w][0]); hi = fmax(hi, sh[w][1]); }
-}
-
-// fp64 -> u64 whose unsigned order is the order of the doubles, and back
-__device__ __forceinline__ unsigned long long dkey(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dkey_value(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
 
 // The SVD of a 3 x 3 matrix by a one-sided Jacobi iteration (Hestenes) on its columns — loss.hip's nuclear_norm3 with V kept: a V = (u_q
 // sigma_q).  On return the columns of a and v are sorted by decreasing norm, sig holds the norms.
@@ -200,9 +115,7 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
   __shared__ double sh_red[WAVES][MAXR];
   __shared__ int sh_cnt[WAVES];
   __shared__ double sh_tf[20];                                       // R (9), c, t (3), q (4), flag
-  __shared__ unsigned sh_hist[2][256];
-  __shared__ unsigned long long sh_prefix[2];
-  __shared__ unsigned sh_rank[2];
+  __shared__ SelectLds sh_sel;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
   const double qnan = __longlong_as_double(0x7ff8000000000000ll);
   double* __restrict__ row = a.stats + (long long)b * DEVO_TRAJ_EVAL_COLS;
@@ -259,17 +172,8 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
     if (flags) { give_up(flags, 0); return; }
   }
 
-  // the estimate's and the ground truth's position and rotation of match k
-  auto match_x = [&](int k) -> V3 { return load_pos(est, est_short ? mi[k] : mj[k]); };
-  auto match_y = [&](int k) -> V3 {
-    if (interp) return V3{ipose[7 * k], ipose[7 * k + 1], ipose[7 * k + 2]};
-    return load_pos(gt, est_short ? mj[k] : mi[k]);
-  };
-  auto match_qx = [&](int k) -> Q4 { return load_quat(est, est_short ? mi[k] : mj[k]); };
-  auto match_qy = [&](int k) -> Q4 {
-    if (interp) return Q4{ipose[7 * k + 3], ipose[7 * k + 4], ipose[7 * k + 5], ipose[7 * k + 6]};
-    return load_quat(gt, est_short ? mj[k] : mi[k]);
-  };
+  // the estimate's and the ground truth's position and rotation of match k (the matches are read back through the pointers that write them)
+  const Matches<T> M(est, gt, mi, mj, ipose, est_short, interp);
 
   // ---- pass 1: association, compaction, the sums of the matched positions
   int n = 0;
@@ -361,7 +265,7 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
   double cov[11] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
   if (aligning)
     for (int k = tid; k < n; k += TB) {
-      const V3 dx = match_x(k) - mx, dy = match_y(k) - my;
+      const V3 dx = M.x(k) - mx, dy = M.y(k) - my;
       cov[0] += dy.x * dx.x; cov[1] += dy.x * dx.y; cov[2] += dy.x * dx.z;
       cov[3] += dy.y * dx.x; cov[4] += dy.y * dx.y; cov[5] += dy.y * dx.z;
       cov[6] += dy.z * dx.x; cov[7] += dy.z * dx.y; cov[8] += dy.z * dx.z;
@@ -428,21 +332,21 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
   const int delta = a.rpe_delta;
   const bool rpe = delta > 0 && delta < n;
   for (int k = tid; k < n; k += TB) {
-    const V3 x = match_x(k), y = match_y(k);
+    const V3 x = M.x(k), y = M.y(k);
     const V3 rx = {R[0] * x.x + R[1] * x.y + R[2] * x.z, R[3] * x.x + R[4] * x.y + R[5] * x.z, R[6] * x.x + R[7] * x.y + R[8] * x.z};
     const double e = norm(y - (c * rx + t));
     err[k] = e;
     if (a.errors_out) a.errors_out[eo + mi[k]] = e;
     sums[0] += e; sums[1] += e * e;
     lo = fmin(lo, e); hi = fmax(hi, e);
-    const Q4 qx = match_qx(k), qy = match_qy(k);
+    const Q4 qx = M.qx(k), qy = M.qy(k);
     const double ang = qangle_deg(qmul(qconj(qy), qmul(qR, qx)));
     sums[2] += ang; sums[3] += ang * ang;
     if (rpe && k + delta < n) {
-      const Q4 qx2 = match_qx(k + delta), qy2 = match_qy(k + delta);
-      const V3 tp = qrot(qconj(qx), c * (match_x(k + delta) - x));   // P_k^-1 P_k+d
+      const Q4 qx2 = M.qx(k + delta), qy2 = M.qy(k + delta);
+      const V3 tp = qrot(qconj(qx), c * (M.x(k + delta) - x));   // P_k^-1 P_k+d
       const Q4 qp = qmul(qconj(qx), qx2);
-      const V3 tq = qrot(qconj(qy), match_y(k + delta) - y);         // Q_k^-1 Q_k+d
+      const V3 tq = qrot(qconj(qy), M.y(k + delta) - y);         // Q_k^-1 Q_k+d
       const Q4 qq = qmul(qconj(qy), qy2);
       const V3 te = qrot(qconj(qq), tp - tq);
       const double ae = qangle_deg(qmul(qconj(qq), qp));
@@ -463,50 +367,11 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
   }
   block_sum(dev, sh_red);
   const int any_nan = __syncthreads_or(nan ? 1 : 0);
-  if (tid == 0) {
-    sh_prefix[0] = sh_prefix[1] = 0ull;
-    sh_rank[0] = (unsigned)((n - 1) / 2); sh_rank[1] = (unsigned)(n / 2);
-  }
-  sh_hist[0][tid] = 0u; sh_hist[1][tid] = 0u;
-  __syncthreads();
-  for (int pass = 0; pass < 8; pass++) {
-    const int shift = 56 - 8 * pass;
-    const unsigned long long p0 = sh_prefix[0], p1 = sh_prefix[1];
-    const unsigned long long mask = pass == 0 ? 0ull : (~0ull << (shift + 8));
-    for (int k = tid; k < n; k += TB) {
-      const unsigned long long key = dkey(err[k]);
-      const unsigned digit = (unsigned)(key >> shift) & 255u;
-      if ((key & mask) == p0) atomicAdd(&sh_hist[0][digit], 1u);
-      if ((key & mask) == p1) atomicAdd(&sh_hist[1][digit], 1u);
-    }
-    __syncthreads();
-    if (tid < 128) {                                                 // waves 0 and 1: one rank each, lane l owns bins 4 l .. 4 l + 3
-      const int r = wv;
-      const unsigned h0 = sh_hist[r][4 * lane], h1 = sh_hist[r][4 * lane + 1], h2 = sh_hist[r][4 * lane + 2], h3 = sh_hist[r][4 * lane + 3];
-      const unsigned sum = h0 + h1 + h2 + h3;
-      unsigned incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const unsigned rank = sh_rank[r];
-      unsigned excl = incl - sum;
-      if (excl <= rank && rank < incl) {                             // exactly one lane
-        unsigned bin = 4u * lane;
-        if (rank >= excl + h0) { excl += h0; bin++; if (rank >= excl + h1) { excl += h1; bin++; if (rank >= excl + h2) { excl += h2; bin++; } } }
-        sh_prefix[r] = (r == 0 ? p0 : p1) | ((unsigned long long)bin << shift);
-        sh_rank[r] = rank - excl;
-      }
-    }
-    __syncthreads();
-    sh_hist[0][tid] = 0u; sh_hist[1][tid] = 0u;
-    __syncthreads();
-  }
+  const double med = block_median<1, false>(err, nullptr, n, n, sh_sel);
 
   if (tid == 0) {
     const bool bad = sums[1] != sums[1];
-    const double median = any_nan ? qnan : 0.5 * (dkey_value(sh_prefix[0]) + dkey_value(sh_prefix[1]));
+    const double median = any_nan ? qnan : med;
     const int terms = rpe ? n - delta : 0;
     row[0] = (double)n;
     row[1] = sqrt(sums[1] * inv_n);
@@ -529,22 +394,9 @@ __global__ __launch_bounds__(TB) void k_traj_eval(const EvalArgs a) {
   }
 }
 
-struct WsLayout { size_t mi, mj, err, ipose, total; };
-WsLayout ws_layout(int64_t total_est, int assoc) {
-  WsLayout L;
-  const size_t n = total_est > 0 ? (size_t)total_est : 0;
-  size_t o = 0;
-  L.mi = o; o += align_up(n * sizeof(int));
-  L.mj = o; o += align_up(n * sizeof(int));
-  L.err = o; o += align_up(n * sizeof(double));
-  L.ipose = o; o += assoc == DEVO_TRAJ_ASSOC_INTERPOLATE ? align_up(n * 7 * sizeof(double)) : 0;
-  L.total = o > 0 ? o : 256;
-  return L;
-}
-
 }  // namespace
 
-extern "C" size_t devo_traj_eval_workspace_bytes(int64_t total_est, int assoc) { return ws_layout(total_est, assoc).total; }
+extern "C" size_t devo_traj_eval_workspace_bytes(int64_t total_est, int assoc) { return eval_ws(total_est, assoc).total; }
 
 extern "C" int devo_traj_eval(const void* est, const void* est_stamps, const int64_t* est_off, int64_t total_est, const void* gt, const void* gt_stamps,
                               const int64_t* gt_off, int64_t total_gt, int B, int pose_dtype, int stamps_f64, int assoc, int align, double max_diff,
@@ -559,7 +411,7 @@ extern "C" int devo_traj_eval(const void* est, const void* est_stamps, const int
   DEVO_REQUIRE(align >= DEVO_TRAJ_ALIGN_NONE && align <= DEVO_TRAJ_ALIGN_SIM3, "traj_eval: unknown alignment %d", align);
   DEVO_REQUIRE(assoc == DEVO_TRAJ_ASSOC_INTERPOLATE || max_diff >= 0.0, "traj_eval: max_diff must be >= 0 (a NaN is refused too)");
   DEVO_REQUIRE(rpe_delta >= 0, "traj_eval: rpe_delta %d", rpe_delta);
-  const WsLayout L = ws_layout(total_est, assoc);
+  const EvalWs L = eval_ws(total_est, assoc);
   if (ws_bytes < L.total || ((uintptr_t)ws & 15)) {
     set_error("traj_eval: workspace of %zu bytes at %p (%zu needed, 16-byte aligned)", ws_bytes, ws, L.total);
     return DEVO_ERR_WORKSPACE;

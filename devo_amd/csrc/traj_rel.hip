@@ -11,17 +11,14 @@
 //      medians by a radix select over the order-preserving 64-bit image of the errors.
 // Every reduction is per-thread strided partials, then wave shuffles, then LDS across the four waves, in a fixed order: no floating-point
 // atomics, bit-reproducible, independent of B and D.  Vector stores only.
-// The reduction, key and quaternion helpers and the select are COPIES of traj_eval.hip's (which stays as it is, listing included).
-#include "common.h"
-#include <math.h>
+// The algebra, the reductions, the select and the evaluation launch's workspace layout are traj_dev.h's, shared with traj_eval.hip.
+#include "traj_dev.h"
 
 namespace {
 
 using namespace devo;
+using namespace devo::traj;
 
-constexpr int TB = 256;
-constexpr int WAVES = TB / 64;
-constexpr int MAXR = 12;                       // values one reduction carries
 constexpr int META = 4;                        // per pair: n, c, u_{n-1} - u_0, flags
 
 struct RelArgs {
@@ -37,145 +34,6 @@ struct RelArgs {
   double* stats; int* status;
 };
 
-struct V3 { double x, y, z; };
-struct Q4 { double x, y, z, w; };
-
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(double s, V3 a) { return {s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ double dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ double norm(V3 a) { return sqrt(dot(a, a)); }
-
-__device__ __forceinline__ Q4 qconj(Q4 q) { return {-q.x, -q.y, -q.z, q.w}; }
-__device__ __forceinline__ Q4 qmul(Q4 a, Q4 b) {
-  return {a.w * b.x + a.x * b.w + a.y * b.z - a.z * b.y, a.w * b.y - a.x * b.z + a.y * b.w + a.z * b.x,
-          a.w * b.z + a.x * b.y - a.y * b.x + a.z * b.w, a.w * b.w - a.x * b.x - a.y * b.y - a.z * b.z};
-}
-// the rotation of a unit quaternion applied to v: v + 2 w (u x v) + 2 u x (u x v)
-__device__ __forceinline__ V3 qrot(Q4 q, V3 v) {
-  const V3 u = {q.x, q.y, q.z};
-  const V3 c = cross(u, v);
-  return v + 2.0 * (q.w * c + cross(u, c));
-}
-// the angle of a unit quaternion's rotation in [0, pi]: well conditioned at 0 and at pi, unlike arccos of the trace
-__device__ __forceinline__ double qangle_rad(Q4 q) { return 2.0 * atan2(sqrt(q.x * q.x + q.y * q.y + q.z * q.z), fabs(q.w)); }
-__device__ __forceinline__ double qangle_deg(Q4 q) { return qangle_rad(q) * (180.0 / 3.14159265358979323846); }
-
-template <typename T> __device__ __forceinline__ V3 load_pos(const T* __restrict__ p, long long i) {
-  return {(double)p[7 * i], (double)p[7 * i + 1], (double)p[7 * i + 2]};
-}
-template <typename T> __device__ __forceinline__ Q4 load_quat(const T* __restrict__ p, long long i) {
-  const double x = (double)p[7 * i + 3], y = (double)p[7 * i + 4], z = (double)p[7 * i + 5], w = (double)p[7 * i + 6];
-  const double r = 1.0 / sqrt(x * x + y * y + z * z + w * w);
-  return {x * r, y * r, z * r, w * r};
-}
-
-// K sums over the workgroup, every thread gets them: shuffles inside a wave, then the four waves' values added in order
-template <int K>
-__device__ __forceinline__ void block_sum(double (&v)[K], double (*sh)[MAXR]) {
-  static_assert(K <= MAXR, "block_sum: too many values");
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] += __shfl_down(v[k], o, 64);
-  }
-  __syncthreads();                                                   // (the previous reduction's values have been read)
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; k++) sh[wv][k] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    double r = sh[0][k];
-#pragma unroll
-    for (int w = 1; w < WAVES; w++) r += sh[w][k];
-    v[k] = r;
-  }
-}
-
-// min and max alike (fmin / fmax skip a NaN; the caller sets both to NaN when the sums are)
-__device__ __forceinline__ void block_minmax(double& lo, double& hi, double (*sh)[MAXR]) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    lo = fmin(lo, __shfl_down(lo, o, 64));
-    hi = fmax(hi, __shfl_down(hi, o, 64));
-  }
-  __syncthreads();
-  if (lane == 0) { sh[wv][0] = lo; sh[wv][1] = hi; }
-  __syncthreads();
-  lo = sh[0][0]; hi = sh[0][1];
-#pragma unroll
-  for (int w = 1; w < WAVES; w++) { lo = fmin(lo, sh[w][0]); hi = fmax(hi, sh[w][1]); }
-}
-
-// fp64 -> u64 whose unsigned order is the order of the doubles, and back
-__device__ __forceinline__ unsigned long long dkey(double d) {
-  const unsigned long long u = (unsigned long long)__double_as_longlong(d);
-  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
-}
-__device__ __forceinline__ double dkey_value(unsigned long long k) {
-  return __longlong_as_double((long long)((k >> 63) ? (k & 0x7fffffffffffffffull) : ~k));
-}
-
-struct SelectLds {
-  unsigned hist[2][256];
-  unsigned long long prefix[2];
-  unsigned rank[2];
-};
-
-// numpy's median of the m values v[2 k] whose ends[k] >= 0, k < n (m >= 1): a radix select, 8-bit digits, an LDS histogram with integer
-// atomics, both middle ranks in the same sweeps.  Every thread gets the result.
-__device__ double block_median(const double* __restrict__ v, const int* __restrict__ ends, int n, int m, SelectLds& s) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  __syncthreads();                                                   // (the previous select's result has been read)
-  if (tid == 0) {
-    s.prefix[0] = s.prefix[1] = 0ull;
-    s.rank[0] = (unsigned)((m - 1) / 2); s.rank[1] = (unsigned)(m / 2);
-  }
-  s.hist[0][tid] = 0u; s.hist[1][tid] = 0u;
-  __syncthreads();
-  for (int pass = 0; pass < 8; pass++) {
-    const int shift = 56 - 8 * pass;
-    const unsigned long long p0 = s.prefix[0], p1 = s.prefix[1];
-    const unsigned long long mask = pass == 0 ? 0ull : (~0ull << (shift + 8));
-    for (int k = tid; k < n; k += TB) {
-      if (ends[k] < 0) continue;
-      const unsigned long long key = dkey(v[2 * (long long)k]);
-      const unsigned digit = (unsigned)(key >> shift) & 255u;
-      if ((key & mask) == p0) atomicAdd(&s.hist[0][digit], 1u);
-      if ((key & mask) == p1) atomicAdd(&s.hist[1][digit], 1u);
-    }
-    __syncthreads();
-    if (tid < 128) {                                                 // waves 0 and 1: one rank each, lane l owns bins 4 l .. 4 l + 3
-      const int r = wv;
-      const unsigned h0 = s.hist[r][4 * lane], h1 = s.hist[r][4 * lane + 1], h2 = s.hist[r][4 * lane + 2], h3 = s.hist[r][4 * lane + 3];
-      const unsigned sum = h0 + h1 + h2 + h3;
-      unsigned incl = sum;
-#pragma unroll
-      for (int o = 1; o < 64; o <<= 1) {
-        const unsigned up = __shfl_up(incl, o, 64);
-        if (lane >= o) incl += up;
-      }
-      const unsigned rank = s.rank[r];
-      unsigned excl = incl - sum;
-      if (excl <= rank && rank < incl) {                             // exactly one lane
-        unsigned bin = 4u * lane;
-        if (rank >= excl + h0) { excl += h0; bin++; if (rank >= excl + h1) { excl += h1; bin++; if (rank >= excl + h2) { excl += h2; bin++; } } }
-        s.prefix[r] = (r == 0 ? p0 : p1) | ((unsigned long long)bin << shift);
-        s.rank[r] = rank - excl;
-      }
-    }
-    __syncthreads();
-    s.hist[0][tid] = 0u; s.hist[1][tid] = 0u;
-    __syncthreads();
-  }
-  return 0.5 * (dkey_value(s.prefix[0]) + dkey_value(s.prefix[1]));
-}
-
 // the leftmost index in [0, n) whose value is >= s (n if there is none)
 __device__ __forceinline__ int lower_bound(const double* __restrict__ u, int n, double s) {
   int lo = 0, hi = n;
@@ -185,33 +43,6 @@ __device__ __forceinline__ int lower_bound(const double* __restrict__ u, int n, 
   }
   return lo;
 }
-
-// what both kernels know of pair b's matches: match k is the estimate's pose ie(k) and the ground truth's pose ig(k) (or interpolated pose k)
-template <typename T>
-struct Matches {
-  const T* est; const T* gt; const int* mi; const int* mj; const double* ipose;
-  bool est_short, interp;
-  __device__ __forceinline__ Matches(const RelArgs& a, int b) {
-    const long long eo = a.est_off[b], e1 = a.est_off[b + 1], go = a.gt_off[b], g1 = a.gt_off[b + 1];
-    interp = a.assoc == DEVO_TRAJ_ASSOC_INTERPOLATE;
-    est_short = interp || (e1 - eo) < (g1 - go);
-    est = static_cast<const T*>(a.est) + 7 * eo;
-    gt = static_cast<const T*>(a.gt) + 7 * go;
-    mi = a.mi + eo; mj = a.mj + eo;
-    ipose = interp ? a.ipose + 7 * eo : nullptr;
-  }
-  __device__ __forceinline__ int ie(int k) const { return est_short ? mi[k] : mj[k]; }
-  __device__ __forceinline__ V3 x(int k) const { return load_pos(est, ie(k)); }
-  __device__ __forceinline__ Q4 qx(int k) const { return load_quat(est, ie(k)); }
-  __device__ __forceinline__ V3 y(int k) const {
-    if (interp) return V3{ipose[7 * (long long)k], ipose[7 * (long long)k + 1], ipose[7 * (long long)k + 2]};
-    return load_pos(gt, est_short ? mj[k] : mi[k]);
-  }
-  __device__ __forceinline__ Q4 qy(int k) const {
-    if (interp) return Q4{ipose[7 * (long long)k + 3], ipose[7 * (long long)k + 4], ipose[7 * (long long)k + 5], ipose[7 * (long long)k + 6]};
-    return load_quat(gt, est_short ? mj[k] : mi[k]);
-  }
-};
 
 // ---- prepare: one workgroup per pair
 template <typename T, typename S>
@@ -376,8 +207,8 @@ __global__ __launch_bounds__(TB) void k_traj_rel_errors(const RelArgs a) {
   }
   block_sum(dev, sh_red);
   const int any_nan = __syncthreads_or(nan ? 1 : 0);
-  const double tmed = block_median(err2, ends, n, m, sh_sel);
-  const double rmed = block_median(err2 + 1, ends, n, m, sh_sel);
+  const double tmed = block_median<2, true>(err2, ends, n, m, sh_sel);
+  const double rmed = block_median<2, true>(err2 + 1, ends, n, m, sh_sel);
 
   if (tid == 0) {
     const bool tbad = sums[2] != sums[2], rbad = sums[4] != sums[4];
@@ -406,7 +237,7 @@ WsLayout ws_layout(int64_t total_est, int assoc, int B, int D) {
   WsLayout L;
   const size_t n = total_est > 0 ? (size_t)total_est : 0, nb = B > 0 ? (size_t)B : 0, nd = D > 0 ? (size_t)D : 0;
   size_t o = 0;
-  L.eval = o; o += align_up(devo_traj_eval_workspace_bytes(total_est, assoc));
+  L.eval = o; o += align_up(eval_ws(total_est, assoc).total);
   L.ev_stats = o; o += align_up(nb * DEVO_TRAJ_EVAL_COLS * sizeof(double));
   L.ev_tf = o; o += align_up(nb * 8 * sizeof(double));
   L.ev_status = o; o += align_up(nb * sizeof(int));
@@ -447,10 +278,11 @@ extern "C" int devo_traj_rel_eval(const void* est, const void* est_stamps, const
   double* ev_stats = reinterpret_cast<double*>(w + L.ev_stats);
   double* ev_tf = reinterpret_cast<double*>(w + L.ev_tf);
   int* ev_status = reinterpret_cast<int*>(w + L.ev_status);
+  const EvalWs E = eval_ws(total_est, assoc);                        // the evaluation launch's own part of the workspace, at L.eval
   // association (and the Umeyama scale): the evaluation launch, which checks every argument it shares with this call
   const int rc = devo_traj_eval(est, est_stamps, est_off, total_est, gt, gt_stamps, gt_off, total_gt, B, pose_dtype, stamps_f64, assoc,
                                 scale_mode == DEVO_TRAJ_REL_SCALE_SIM3 ? DEVO_TRAJ_ALIGN_SIM3 : DEVO_TRAJ_ALIGN_NONE, max_diff, 0, ev_stats, ev_tf, ev_status,
-                                nullptr, nullptr, w + L.eval, devo_traj_eval_workspace_bytes(total_est, assoc), stream);
+                                nullptr, nullptr, w + L.eval, E.total, stream);
   if (rc != DEVO_OK) return rc;
 
   RelArgs a;
@@ -459,11 +291,8 @@ extern "C" int devo_traj_rel_eval(const void* est, const void* est_stamps, const
   a.assoc = assoc; a.unit = unit; a.relative = relative ? 1 : 0; a.along = along; a.end = end; a.scale_mode = scale_mode; a.D = D;
   a.scale = scale; a.scale_v = scale_per_pair;
   for (int d = 0; d < DEVO_TRAJ_REL_MAX_DELTAS; d++) a.deltas[d] = d < D ? deltas[d] : 0.0;
-  // the evaluation's own layout of its workspace (traj_eval.hip: mi, mj, err, ipose, each aligned)
-  const size_t n = (size_t)total_est;
-  const size_t o_mj = align_up(n * sizeof(int)), o_ipose = 2 * o_mj + align_up(n * sizeof(double));
-  a.mi = reinterpret_cast<const int*>(w + L.eval); a.mj = reinterpret_cast<const int*>(w + L.eval + o_mj);
-  a.ipose = reinterpret_cast<const double*>(w + L.eval + o_ipose);
+  a.mi = reinterpret_cast<const int*>(w + L.eval + E.mi); a.mj = reinterpret_cast<const int*>(w + L.eval + E.mj);
+  a.ipose = reinterpret_cast<const double*>(w + L.eval + E.ipose);
   a.ev_stats = ev_stats; a.ev_tf = ev_tf; a.ev_status = ev_status;
   a.u = reinterpret_cast<double*>(w + L.u); a.meta = reinterpret_cast<double*>(w + L.meta);
   a.err2 = errors_out ? errors_out : reinterpret_cast<double*>(w + L.err2);

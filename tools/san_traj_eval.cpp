@@ -1,8 +1,9 @@
-// Stand-alone host check of devo_traj_eval's argument handling (csrc/traj_eval.hip) under AddressSanitizer and UBSan: every call below is
-// refused before the launch, so the program needs no GPU.  Host code only; from the repository root:
+// Stand-alone host check of devo_traj_eval's and devo_traj_rel_eval's argument handling (csrc/traj_eval.hip, csrc/traj_rel.hip, their shared
+// csrc/traj_dev.h) under AddressSanitizer and UBSan: every call below is refused before the launch, so the program needs no GPU.  Host code
+// only; from the repository root:
 //   hipcc --offload-arch=gfx950 -O1 -g -std=c++17 -Xarch_host -fsanitize=address,undefined -Xarch_host -fno-sanitize-recover=undefined \
-//         devo_amd/csrc/traj_eval.hip tools/san_traj_eval.cpp -o /tmp/san_traj_eval && /tmp/san_traj_eval
-// prints the 13 refusals and "0 unexpected return codes" (exit status = the number of unexpected ones; a sanitizer report aborts).
+//         devo_amd/csrc/traj_eval.hip devo_amd/csrc/traj_rel.hip tools/san_traj_eval.cpp -o /tmp/san_traj_eval && /tmp/san_traj_eval
+// prints the 13 + 20 refusals and "0 unexpected return codes" (exit status = the number of unexpected ones; a sanitizer report aborts).
 #include <cstdio>
 #include <cstdint>
 #include <cstdarg>
@@ -33,6 +34,50 @@ int main() {
   bad += call(1, 8, 8, DEVO_F64, 0, 2, 1.0, -1, d, off, d, d, need) != DEVO_ERR_ARG;           // negative rpe_delta
   bad += call(1, 8, 8, DEVO_F64, 0, 2, 1.0, 0, d, off, d, d, need - 1) != DEVO_ERR_WORKSPACE;  // short workspace
   bad += call(1, 8, 8, DEVO_F64, 0, 2, 1.0, 0, d, off, d, (char*)d + 8, need) != DEVO_ERR_WORKSPACE;   // misaligned workspace
+
+  // ---- devo_traj_rel_eval: its workspace holds the evaluation launch's, whatever the association; a negative total counts as empty
+  for (int assoc : {DEVO_TRAJ_ASSOC_NEAREST, DEVO_TRAJ_ASSOC_INTERPOLATE}) {
+    bad += devo_traj_rel_workspace_bytes(8, assoc, 1, 2) < devo_traj_eval_workspace_bytes(8, assoc);
+    bad += devo_traj_rel_workspace_bytes(-5, assoc, 1, 2) != devo_traj_rel_workspace_bytes(0, assoc, 1, 2);
+  }
+  alignas(16) static char wsb[32768];
+  const size_t rneed = devo_traj_rel_workspace_bytes(8, DEVO_TRAJ_ASSOC_NEAREST, 1, 2);
+  bad += rneed + 8 > sizeof(wsb);
+  struct Rel {
+    int B = 1, D = 2, dtype = DEVO_F64, unit = DEVO_TRAJ_REL_UNIT_FRAMES, along = DEVO_TRAJ_REL_ALONG_GT, end = DEVO_TRAJ_REL_END_REACH;
+    int mode = DEVO_TRAJ_REL_SCALE_VALUE;
+    int64_t ne = 8;
+    double scale = 1.0, delta1 = 2.0;
+    bool no_deltas = false, no_stats = false;
+    const double* scale_v = nullptr;
+    size_t short_by = 0, shift = 0;
+  };
+  auto rel = [&](const Rel& r) {
+    double deltas[DEVO_TRAJ_REL_MAX_DELTAS + 1];
+    for (double& x : deltas) x = 1.0;
+    deltas[1] = r.delta1;
+    return devo_traj_rel_eval(d, d, off, r.ne, d, d, off, 8, r.B, r.dtype, 0, DEVO_TRAJ_ASSOC_NEAREST, 1.0, r.no_deltas ? nullptr : deltas, r.D, r.unit, 0, r.along,
+                              r.end, r.mode, r.scale, r.scale_v, r.no_stats ? nullptr : d, st, nullptr, nullptr, wsb + r.shift, rneed - r.short_by, nullptr);
+  };
+  const double inf = __builtin_inf();
+  Rel r;
+  r = Rel(); r.B = 0; bad += rel(r) != DEVO_ERR_ARG;                                           // no pair
+  r = Rel(); r.D = 0; bad += rel(r) != DEVO_ERR_ARG;                                           // no delta
+  r = Rel(); r.D = DEVO_TRAJ_REL_MAX_DELTAS + 1; bad += rel(r) != DEVO_ERR_ARG;                // too many deltas
+  r = Rel(); r.no_deltas = true; bad += rel(r) != DEVO_ERR_ARG;                                // null deltas
+  for (double x : {0.0, -1.0, inf, nan}) { r = Rel(); r.delta1 = x; bad += rel(r) != DEVO_ERR_ARG; }   // a delta of 0, negative, inf, NaN
+  r = Rel(); r.unit = DEVO_TRAJ_REL_UNIT_DEGREES + 1; bad += rel(r) != DEVO_ERR_ARG;           // unknown unit
+  r = Rel(); r.along = 2; bad += rel(r) != DEVO_ERR_ARG;                                       // unknown along
+  r = Rel(); r.end = 2; bad += rel(r) != DEVO_ERR_ARG;                                         // unknown end rule
+  r = Rel(); r.mode = DEVO_TRAJ_REL_SCALE_PER_PAIR + 1; bad += rel(r) != DEVO_ERR_ARG;         // unknown scale mode
+  r = Rel(); r.scale = 0.0; bad += rel(r) != DEVO_ERR_ARG;                                     // a given scale of 0
+  r = Rel(); r.scale = inf; bad += rel(r) != DEVO_ERR_ARG;                                     // and of inf
+  r = Rel(); r.mode = DEVO_TRAJ_REL_SCALE_PER_PAIR; bad += rel(r) != DEVO_ERR_ARG;             // per-pair scales missing
+  r = Rel(); r.no_stats = true; bad += rel(r) != DEVO_ERR_ARG;                                 // no output
+  r = Rel(); r.ne = -1; bad += rel(r) != DEVO_ERR_ARG;                                         // negative total
+  r = Rel(); r.short_by = 1; bad += rel(r) != DEVO_ERR_WORKSPACE;                              // short workspace
+  r = Rel(); r.shift = 8; bad += rel(r) != DEVO_ERR_WORKSPACE;                                 // misaligned workspace
+  r = Rel(); r.dtype = DEVO_F16; bad += rel(r) != DEVO_ERR_ARG;                                // fp16 poses: the inner devo_traj_eval's refusal
   printf("%d unexpected return codes\n", bad);
   return bad;
 }
